@@ -27,6 +27,25 @@ in config 4) -- blocks and shards are independent, so there is no data-path
 collective; RCCL carries only the barrier, the max of the per-rank times and
 the sum of bytes.  value = total uncompressed bytes of all ranks / max time.
 
+A plain run does only what the headline figure needs: it fills the inputs,
+runs the warmup steps, times `--steps` steps, writes the last step's outputs
+when `--dump-outputs DIR` is given, and prints the result line.  `--full` adds
+everything else around the same timed steps: the parity gate before timing
+(exact round trip + the reference's committed digests), the per-kernel HIP-event
+breakdown and the dominant kernel's roofline, the device-copy bandwidth and the
+CPU baseline (`--no-prof` / `--no-cpu-baseline` leave those two out of a
+`--full` run); a plain line carries null in their places.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of
+the timed path receives it, to DIR/<name>.npy (rank 0; DIR/<name>_rank<R>.npy
+on the other ranks): the compressed stream(s) up to their length and the
+decoded array(s) (config 1: the shuffled and the unshuffled array) as float32,
+or float64 for 4-byte integers, and the stream length(s) as float64.  An array
+of more than DUMP_ELEMS elements is written as a fixed sample of that many (its
+first and last element and sorted indices drawn from a seeded generator), at
+most 16 MiB per file.  The inputs depend only on the arguments, so two builds
+of the library can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -71,13 +90,22 @@ def parse_args(argv=None):
                     help="configs 2/3: read the same synthetic bytes as elements of this many bytes")
     ap.add_argument("--block-size", type=int, default=None,
                     help="configs 2/3: block size in elements (0 = the reference's default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity gate before timing, the per-kernel event timing and "
+                         "roofline, the device-copy bandwidth and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--cpu-sample-mib", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="skip per-kernel event timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-prof", action="store_true",
+                    help="--full: skip per-kernel event timing")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group (RCCL on a GPU) and run the barrier / "
                          "MAX / SUM collectives even at world size 1 (tests the N>1 code path)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ----------------------------------------------------------------- dist utils
@@ -263,6 +291,50 @@ def check_digests(pairs, world, device):
     if max_over_ranks(1.0 if bad else 0.0, world, device) > 0:
         raise SystemExit(3)
     return sorted({n for n, _, _, _ in pairs})
+
+
+# ------------------------------------------------------------- output dumping
+DUMP_ELEMS = 2 << 20  # elements per dumped array (16 MiB as float64); larger ones are sampled
+DUMP_SEED = 20240
+
+
+def sample_indices(m, k, seed):
+    """k sorted indices into an array of m > k elements: its first and last
+    element and seeded draws in between -- the same for every run."""
+    import numpy as np
+    idx = np.random.default_rng(seed).integers(0, m, size=k, dtype=np.int64)
+    idx[0], idx[-1] = 0, m - 1
+    idx.sort()
+    return idx
+
+
+def dump_outputs(dirpath, arrays, rank):
+    """arrays: [(name, pieces)], pieces a list of 1-D device tensors (one per
+    stream or chunk, already cut to their valid length) or a list of numbers.
+    Each name becomes one .npy file: the pieces' elements, or a sample of
+    DUMP_ELEMS // len(pieces) of them for a longer piece, one after another."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    written = {}
+    for name, pieces in arrays:
+        if not isinstance(pieces[0], torch.Tensor):
+            out = np.asarray(pieces, dtype=np.float64)
+        else:
+            per = max(DUMP_ELEMS // len(pieces), 2)
+            wide = pieces[0].dtype in (torch.int32, torch.int64, torch.float64)
+            parts = []
+            for i, t in enumerate(pieces):
+                t = t.reshape(-1)
+                if t.numel() > per:
+                    idx = torch.from_numpy(sample_indices(t.numel(), per, DUMP_SEED + i))
+                    t = t[idx.to(t.device)]
+                parts.append(t.cpu().numpy().astype(np.float64 if wide else np.float32))
+            out = np.concatenate(parts)
+        fn = name + (".npy" if rank == 0 else "_rank%d.npy" % rank)
+        np.save(os.path.join(dirpath, fn), out)
+        written[fn] = [str(out.dtype), int(out.size)]
+    return written
 
 
 # ---------------------------------------------------------------- CPU baseline
@@ -455,6 +527,10 @@ def main(argv=None):
             lengths()
             return (state["dres"].cpu().tolist() == state["counts"]
                     and all(torch.equal(x, y) for x, y in zip(xs, ys)))
+
+        def outputs():  # after lengths()
+            return [("compressed", [o[:c] for o, c in zip(outs, state["counts"])]),
+                    ("compressed_len", state["counts"]), ("decoded", ys)]
         workload = ("batch of %d independent %d MiB %s G1 chunks per GPU (seed 12345 + global "
                     "chunk id), default 8 KiB blocks, bshuf_*_lz4_batch_dev: one launch per kernel "
                     "for all chunks, device-resident, decoder rebuilds each chunk's block index"
@@ -477,6 +553,9 @@ def main(argv=None):
 
         def check():
             return torch.equal(x, y)
+
+        def outputs():
+            return [("shuffled", [s_buf]), ("unshuffled", [y])]
         workload = ("bshuf_bitshuffle + bshuf_bitunshuffle of a %.3g MiB %s ramp (G0), default "
                     "blocks, device-resident" % (nbytes / (1 << 20), cfg["dtype"]))
     elif args.elem_size or args.block_size:
@@ -523,6 +602,10 @@ def main(argv=None):
         def check():
             lengths()
             return int(res_d.item()) == state["C"] and torch.equal(x, y)
+
+        def outputs():  # after lengths()
+            return [("compressed", [comp[:state["C"]]]), ("compressed_len", [state["C"]]),
+                    ("decoded", [y])]
         workload = ("bitshuffle+LZ4 encode+decode round trip, %.3g GiB of %s %s bytes per GPU read as "
                     "%d-byte elements, block size %d elements (%d bytes), device-resident, decoder "
                     "rebuilds the block index" % (
@@ -555,57 +638,64 @@ def main(argv=None):
         def check():
             lengths()
             return int(res_d.item()) == state["C"] and torch.equal(x, y)
+
+        def outputs():  # after lengths()
+            return [("compressed", [comp[:state["C"]]]), ("compressed_len", [state["C"]]),
+                    ("decoded", [y])]
         workload = ("bitshuffle+LZ4 encode+decode round trip, %.3g GiB %s %s per GPU, default "
                     "blocks (%d elem), device-resident, decoder rebuilds the block index" % (
                         gib, cfg["dtype"], "G1 correlated noise" if cfg["gen"] == 1
                         else "G2 smooth field", B.default_block_size(es)))
 
-    # parity gate before timing: exact round trip, and on every rank that owns
+    # --full: parity gate before timing: exact round trip, and on every rank that owns
     # a BASELINE input with a committed reference digest, the input and the
     # framed stream byte-for-byte against the REFERENCE's output (length +
     # SHA-256).  Any mismatch exits non-zero before anything is timed.
-    step()
-    torch.cuda.synchronize()
-    if not check():
-        raise SystemExit("round trip parity FAILED on rank %d" % rank)
-    digests, pairs = load_digests(), []
-    if cfg["what"] == "shuffle" and rank == 0 and gib == cfg["gib"]:
-        d = digests["cfg1_g0_i32_64MiB"]
-        pairs += [(d["name"], "input_sha256", sha256_dev(x), d["input_sha256"]),
-                  (d["name"], "shuffled_sha256", sha256_dev(s_buf), d["shuffled_sha256"])]
-    elif cfg["what"] == "lz4" and rank == 0 and gib == cfg["gib"] and not (args.elem_size or args.block_size):
-        d = digests["cfg2_g1_i16_4GiB" if args.config == 2 else "cfg3_g2_f32_16GiB"]
-        pairs += [(d["name"], "input_sha256", sha256_dev(x), d["input_sha256"]),
-                  (d["name"], "compressed_len", state["C"], d["compressed_len"]),
-                  (d["name"], "compressed_sha256", sha256_dev(comp, state["C"]),
-                   d["compressed_sha256"])]
-    elif cfg["what"] == "lz4" and rank == 0 and (args.elem_size or args.block_size):
-        d = mode_digest(digests, cfg["gen"], es, args.block_size or 0, nbytes)
-        if d is not None:
+    parity = None
+    if args.full:
+        step()
+        torch.cuda.synchronize()
+        if not check():
+            raise SystemExit("round trip parity FAILED on rank %d" % rank)
+        digests, pairs = load_digests(), []
+        if cfg["what"] == "shuffle" and rank == 0 and gib == cfg["gib"]:
+            d = digests["cfg1_g0_i32_64MiB"]
+            pairs += [(d["name"], "input_sha256", sha256_dev(x), d["input_sha256"]),
+                      (d["name"], "shuffled_sha256", sha256_dev(s_buf), d["shuffled_sha256"])]
+        elif cfg["what"] == "lz4" and rank == 0 and gib == cfg["gib"] and not (args.elem_size or args.block_size):
+            d = digests["cfg2_g1_i16_4GiB" if args.config == 2 else "cfg3_g2_f32_16GiB"]
             pairs += [(d["name"], "input_sha256", sha256_dev(x), d["input_sha256"]),
                       (d["name"], "compressed_len", state["C"], d["compressed_len"]),
                       (d["name"], "compressed_sha256", sha256_dev(comp, state["C"]),
                        d["compressed_sha256"])]
-    elif cfg["what"] == "batch" and cfg["chunk_mib"] == 32:
-        for i in range(nchunks):
-            name = "cfg4_g1_chunk%04d" % (rank * nchunks + i)
-            if name in digests:
-                d = digests[name]
-                c = state["counts"][i]
-                pairs += [(name, "compressed_len", c, d["compressed_len"]),
-                          (name, "compressed_sha256", sha256_dev(outs[i], c), d["compressed_sha256"])]
-    checked = check_digests(pairs, world, dev)
-    parity = {"kind": "reference-digest" if checked else "self-round-trip",
-              "round_trip_exact": True, "digests_matched": checked,
-              "source": "tests/golden/vectors.json (reference C output, SHA-256 + length)"}
+        elif cfg["what"] == "lz4" and rank == 0 and (args.elem_size or args.block_size):
+            d = mode_digest(digests, cfg["gen"], es, args.block_size or 0, nbytes)
+            if d is not None:
+                pairs += [(d["name"], "input_sha256", sha256_dev(x), d["input_sha256"]),
+                          (d["name"], "compressed_len", state["C"], d["compressed_len"]),
+                          (d["name"], "compressed_sha256", sha256_dev(comp, state["C"]),
+                           d["compressed_sha256"])]
+        elif cfg["what"] == "batch" and cfg["chunk_mib"] == 32:
+            for i in range(nchunks):
+                name = "cfg4_g1_chunk%04d" % (rank * nchunks + i)
+                if name in digests:
+                    d = digests[name]
+                    c = state["counts"][i]
+                    pairs += [(name, "compressed_len", c, d["compressed_len"]),
+                              (name, "compressed_sha256", sha256_dev(outs[i], c), d["compressed_sha256"])]
+        checked = check_digests(pairs, world, dev)
+        parity = {"kind": "reference-digest" if checked else "self-round-trip",
+                  "round_trip_exact": True, "digests_matched": checked,
+                  "source": "tests/golden/vectors.json (reference C output, SHA-256 + length)"}
 
-    # HIP-event timing: every kernel during the warmup steps (the per-kernel
+    # --full: HIP-event timing: every kernel during the warmup steps (the per-kernel
     # breakdown), then ONLY the dominant kernel during the timed steps (the
     # roofline's average launch) -- each timed launch adds two event records
     # to its stream, ~0.2 ms per config-2 step when every kernel is timed
     kern_all, kern = {}, {}
     warm = args.warmup
-    if not args.no_prof:
+    prof = args.full and not args.no_prof
+    if prof:
         lib.bshuf_prof_enable(1)
         prof_collect(lib)  # reset
         if warm > 0:
@@ -619,7 +709,7 @@ def main(argv=None):
             lib.bshuf_prof_only(dom_name.encode())
             warm = 0
     elapsed = timed_loop(step, args.steps, warm, world, torch.cuda.synchronize, dev)
-    if not args.no_prof:
+    if prof:
         kern = prof_collect(lib)
         lib.bshuf_prof_only(None)
         lib.bshuf_prof_enable(0)
@@ -631,6 +721,7 @@ def main(argv=None):
     total_bytes = sum_over_ranks(float(nbytes) * args.steps, world, dev)
     value = total_bytes / elapsed / GIB
     ms_step = elapsed / args.steps * 1e3
+    dumped = dump_outputs(args.dump_outputs, outputs(), rank) if args.dump_outputs else None
 
     roofline = None
     kernels = {}
@@ -683,7 +774,7 @@ def main(argv=None):
     stage = {"alg_GBps_per_gpu": round(rt, 1), "roofline_frac": round(rt / HBM_PEAK_GBS, 4)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args.cpu_sample_mib, cfg)
         except Exception as e:  # reported, never fatal for the GPU line
@@ -699,7 +790,7 @@ def main(argv=None):
             "metric": metric, "value": round(value, 3), "unit": "GiB/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full, "dumped": dumped,
             "config": {"workload": workload, "baseline_config": args.config,
                        "elem_size": es, "block_size": args.block_size or B.default_block_size(es),
                        "bytes_per_gpu": nbytes, "compressed_bytes_rank0": C,
@@ -716,7 +807,8 @@ def main(argv=None):
                                     for k, v in kern_all.items() if not overlapped(k)},
             "kernels_ms_per_step_overlapped": {k: round(v[1] / breakdown_steps, 4)
                                                for k, v in kern_all.items() if overlapped(k)},
-            "kernels_timed_in": "warmup steps" if args.warmup > 0 else "timed steps",
+            "kernels_timed_in": (None if not prof else
+                                 "warmup steps" if args.warmup > 0 else "timed steps"),
             "parity": parity, "cpu_baseline": cpu, "dist": dist_info(),
         }
         print(json.dumps(line), flush=True)

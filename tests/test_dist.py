@@ -74,6 +74,47 @@ def test_bench_args_default_to_one_gpu():
     assert bench.CONFIGS[2]["gib"] == 4.0 and bench.CONFIGS[2]["dtype"] == "int16"
 
 
+def test_bench_plain_by_default_and_steps_checked():
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "0"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 0
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """Arrays up to DUMP_ELEMS elements are written whole, longer ones as the
+    same seeded sample on every call (first and last element included); 4-byte
+    integers and lengths go to float64, narrower types to float32; several
+    pieces share the budget and follow one another; other ranks get a suffix."""
+    import numpy as np
+    import torch
+
+    import bench
+    monkeypatch.setattr(bench, "DUMP_ELEMS", 1000)
+    small = torch.arange(1000, dtype=torch.int16) - 500
+    big = torch.arange(5001, dtype=torch.int32) * 100003
+    pieces = [torch.arange(700, dtype=torch.uint8), torch.arange(100, dtype=torch.uint8)]
+    arrays = [("small", [small]), ("big", [big]), ("pieces", pieces), ("lens", [700, 100])]
+    w = bench.dump_outputs(str(tmp_path / "a"), arrays, 0)
+    assert w == {"small.npy": ["float32", 1000], "big.npy": ["float64", 1000],
+                 "pieces.npy": ["float32", 600], "lens.npy": ["float64", 2]}
+    s, b, p, l = (np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("small", "big", "pieces", "lens"))
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy())
+    idx = bench.sample_indices(5001, 1000, bench.DUMP_SEED)
+    assert idx[0] == 0 and idx[-1] == 5000 and np.all(np.diff(idx) >= 0)
+    assert b.dtype == np.float64 and np.array_equal(b, big.numpy()[idx])  # exact above 2^24
+    i0 = bench.sample_indices(700, 500, bench.DUMP_SEED)
+    assert np.array_equal(p, np.concatenate([pieces[0].numpy()[i0], pieces[1].numpy()]))
+    assert l.dtype == np.float64 and l.tolist() == [700.0, 100.0]
+    bench.dump_outputs(str(tmp_path / "b"), arrays, 3)
+    assert sorted(os.listdir(str(tmp_path / "b"))) == ["big_rank3.npy", "lens_rank3.npy",
+                                                        "pieces_rank3.npy", "small_rank3.npy"]
+    assert np.array_equal(np.load(str(tmp_path / "b" / "big_rank3.npy")), b)
+
+
 def test_bench_gpus_spawns_ranks_and_checks_world(monkeypatch):
     """--gpus N outside torch.distributed re-launches bench.py under
     torch.distributed.run with N ranks (as a child process, exiting with its

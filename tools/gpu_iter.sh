@@ -7,14 +7,15 @@ TAG=${1:-it}
 K=${2:-}
 AB=${3:-0,2}
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+export OUT=${OUT:-bench_out}  # results directory
+mkdir -p $OUT
 KARG=()
 [ -n "$K" ] && KARG=(-k "$K")
-timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 600 --timeout-method thread -p no:cacheprovider "${KARG[@]}" > gpurun_out/${TAG}_pytest.log 2>&1 && \
-timeout -k 10 300 python -u tools/ab.py $AB 2 1 3 > gpurun_out/${TAG}_ab.log 2>&1 && \
-timeout -k 10 300 python -u tools/ab.py $AB 2 2 2 > gpurun_out/${TAG}_ab_g2.log 2>&1 && \
-timeout -k 10 300 python -u bench.py --no-cpu-baseline > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 600 --timeout-method thread -p no:cacheprovider "${KARG[@]}" > $OUT/${TAG}_pytest.log 2>&1 && \
+timeout -k 10 300 python -u tools/ab.py $AB 2 1 3 > $OUT/${TAG}_ab.log 2>&1 && \
+timeout -k 10 300 python -u tools/ab.py $AB 2 2 2 > $OUT/${TAG}_ab_g2.log 2>&1 && \
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 rc=$?
-tail -4 gpurun_out/${TAG}_pytest.log
-cat gpurun_out/${TAG}_ab.log gpurun_out/${TAG}_ab_g2.log gpurun_out/${TAG}_bench.json 2>/dev/null
+tail -4 $OUT/${TAG}_pytest.log
+cat $OUT/${TAG}_ab.log $OUT/${TAG}_ab_g2.log $OUT/${TAG}_bench.json 2>/dev/null
 exit $rc

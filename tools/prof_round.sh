@@ -7,11 +7,12 @@
 set -o pipefail
 TAG=${1:-r}
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
+export OUT=${OUT:-bench_out}  # results directory
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_prof -o run -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/${TAG}_prof_bench.json 2> gpurun_out/${TAG}_prof.err && \
+mkdir -p $OUT
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -o run -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_prof_bench.json 2> $OUT/${TAG}_prof.err && \
 bash tools/pmc.sh ${TAG}_pmc_g1 4 tools/pmc_sets.txt 1 && \
 bash tools/pmc.sh ${TAG}_pmc_g2 4 tools/pmc_sets.txt 2
 rc=$?
-cat gpurun_out/${TAG}_prof_bench.json 2>/dev/null
+cat $OUT/${TAG}_prof_bench.json 2>/dev/null
 exit $rc
