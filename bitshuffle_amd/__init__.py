@@ -10,6 +10,8 @@ Host (numpy) functions
     bitshuffle(arr, block_size=0)            -> array, same shape/dtype
     bitunshuffle(arr, block_size=0)          -> array
     compress_lz4(arr, block_size=0)          -> uint8 array (framed stream)
+        mode="fast" (here and in the device compress functions): the fast
+        parse FAST_PARSE_VERSION -- same format, not the reference's bytes
     decompress_lz4(arr, shape, dtype, block_size=0) -> array
 Device (torch CUDA/HIP tensor) functions, no host round trip
     bitshuffle_dev / bitunshuffle_dev / compress_lz4_dev / decompress_lz4_dev
@@ -26,6 +28,7 @@ from ._lib import (  # noqa: F401
     using_SSE2,
 )
 from .api import (  # noqa: F401
+    FAST_PARSE_VERSION,
     bitshuffle,
     bitshuffle_dev,
     bitunshuffle,
@@ -61,4 +64,5 @@ __all__ = [
     "decompress_lz4_dev",
     "compress_lz4_batch_dev",
     "decompress_lz4_batch_dev",
+    "FAST_PARSE_VERSION",
 ]

@@ -44,6 +44,11 @@ PROTOTYPES = {
     "bshuf_decompress_lz4_batch_dev": (_i64, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp]),
     "bshuf_decompress_lz4_batch_dev_dlen": (_i64, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz,
                                                    _vp, _vp]),
+    "bshuf_lz4_fast_version": (_int, []),
+    "bshuf_compress_lz4_fast": (_i64, [_vp, _vp, _sz, _sz, _sz]),
+    "bshuf_compress_lz4_fast_dev": (_i64, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "bshuf_compress_lz4_fast_batch_dev": (_i64, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp,
+                                                 _vp]),
     "bshuf_synth_fill_dev": (_i64, [_vp, _sz, _int, _u64, _u64, _vp]),
     "bshuf_prof_enable": (None, [_int]),
     "bshuf_prof_only": (None, [ctypes.c_char_p]),

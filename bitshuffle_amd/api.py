@@ -70,9 +70,25 @@ def bitunshuffle(arr, block_size=0, out=None):
     return out
 
 
-def compress_lz4(arr, block_size=0, out=None):
+# The parse rule mode="fast" follows ("fast parse v1").
+FAST_PARSE_VERSION = int(lib.bshuf_lz4_fast_version())
+
+
+def _mode(mode, exact, fast):
+    """The entry point of an encode mode: "exact" (the reference encoder's
+    bytes) or "fast" (same format, fixed-offset parse, other bytes)."""
+    if mode == "exact":
+        return exact
+    if mode == "fast":
+        return fast
+    raise ValueError("mode must be 'exact' or 'fast', not %r" % (mode,))
+
+
+def compress_lz4(arr, block_size=0, out=None, mode="exact"):
     """Bitshuffle then LZ4-compress; returns the framed uint8 stream
-    (reference bitshuffle/ext.pyx:401-447)."""
+    (reference bitshuffle/ext.pyx:401-447).  mode="fast": the fast parse
+    (any bitshuffle/LZ4 reader decodes it; not the reference encoder's bytes)."""
+    fn = _mode(mode, lib.bshuf_compress_lz4, lib.bshuf_compress_lz4_fast)
     if not arr.flags["C_CONTIGUOUS"]:
         raise ValueError("Input array must be C-contiguous.")
     size, itemsize = arr.size, arr.dtype.itemsize
@@ -80,7 +96,7 @@ def compress_lz4(arr, block_size=0, out=None):
     if bound > (1 << 62):  # the (size_t)-81 quirk of an invalid block size
         _fail(-81)
     out = _make_array((max(bound, 1),), np.uint8, out)
-    count = _check(lib.bshuf_compress_lz4(_ptr(arr), _ptr(out), size, itemsize, block_size))
+    count = _check(fn(_ptr(arr), _ptr(out), size, itemsize, block_size))
     return out[:count]
 
 
@@ -160,13 +176,14 @@ def _elems(t, elem_size):
 
 
 def compress_lz4_dev(t, block_size=0, out=None, workspace=None, result=None, offsets=None,
-                     stream=None, sync=True, elem_size=None):
+                     stream=None, sync=True, elem_size=None, mode="exact"):
     """Device-resident bshuf_compress_lz4.  Returns the framed stream as a uint8
     tensor view (sync=True), or (out, result) where result is a 1-element int64
     device tensor holding the byte count / error (sync=False).  `elem_size`
     overrides the tensor's element size (any E, e.g. a uint8 tensor of
-    7-byte records)."""
+    7-byte records).  mode="fast" selects bshuf_compress_lz4_fast_dev."""
     torch = _torch()
+    fn = _mode(mode, lib.bshuf_compress_lz4_dev, lib.bshuf_compress_lz4_fast_dev)
     n, es = _elems(t, elem_size)
     bound = compress_lz4_bound(n, es, block_size)
     if bound > (1 << 62):
@@ -178,8 +195,7 @@ def compress_lz4_dev(t, block_size=0, out=None, workspace=None, result=None, off
     ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
     wsb = workspace.numel() if workspace is not None else 0
     offp = _dptr(offsets) if offsets is not None else None
-    _check(lib.bshuf_compress_lz4_dev(_dptr(t), _dptr(out), n, es, block_size, ws, wsb,
-                                      _dptr(result), offp, _stream(stream)))
+    _check(fn(_dptr(t), _dptr(out), n, es, block_size, ws, wsb, _dptr(result), offp, _stream(stream)))
     if not sync:
         return out, result
     count = int(result.item())
@@ -267,13 +283,15 @@ def _size_array(vals):
 
 
 def compress_lz4_batch_dev(tensors, block_size=0, outs=None, workspace=None, offsets=None,
-                           stream=None, sync=True, elem_size=None):
+                           stream=None, sync=True, elem_size=None, mode="exact"):
     """bshuf_compress_lz4_batch_dev over a list of device tensors (same dtype):
     one launch per kernel for all of them.  Returns the list of framed uint8
     streams (sync=True), or (outs, results) with results a device int64 tensor
     of per-stream byte counts / error codes.  `elem_size` overrides the
-    tensors' element size (as in compress_lz4_dev)."""
+    tensors' element size (as in compress_lz4_dev).  mode="fast" selects
+    bshuf_compress_lz4_fast_batch_dev."""
     torch = _torch()
+    fn = _mode(mode, lib.bshuf_compress_lz4_batch_dev, lib.bshuf_compress_lz4_fast_batch_dev)
     if not tensors:
         return []
     es = _elems(tensors[0], elem_size)[1]
@@ -292,8 +310,8 @@ def compress_lz4_batch_dev(tensors, block_size=0, outs=None, workspace=None, off
     ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
     wsb = workspace.numel() if workspace is not None else 0
     offp = _dptr(offsets) if offsets is not None else None
-    _check(lib.bshuf_compress_lz4_batch_dev(pin, pout, psz, len(tensors), es, block_size, ws, wsb,
-                                            _dptr(results), offp, _stream(stream)))
+    _check(fn(pin, pout, psz, len(tensors), es, block_size, ws, wsb, _dptr(results), offp,
+              _stream(stream)))
     if not sync:
         return outs, results
     counts = results.cpu().tolist()

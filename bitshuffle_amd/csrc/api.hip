@@ -221,9 +221,9 @@ size_t bshuf_compress_lz4_dev_workspace(size_t size, size_t elem_size, size_t bl
     return enc_ws(p, nullptr, nullptr);
 }
 
-int64_t bshuf_compress_lz4_dev(const void* in, void* out, size_t size, size_t elem_size,
-                               size_t block_size, void* ws, size_t ws_bytes, int64_t* d_result,
-                               uint64_t* block_offsets, void* stream) {
+static int64_t compress_dev(const void* in, void* out, size_t size, size_t elem_size,
+                            size_t block_size, void* ws, size_t ws_bytes, int64_t* d_result,
+                            uint64_t* block_offsets, void* stream, bool fast) {
     Plan p;
     const int64_t r = make_plan(size, elem_size, block_size, p);
     if (r) return r;
@@ -239,7 +239,7 @@ int64_t bshuf_compress_lz4_dev(const void* in, void* out, size_t size, size_t el
     }
     EncodeBufs b;
     enc_ws(p, &b, (uint8_t*)ws);
-    if (launch_encode((const uint8_t*)in, (uint8_t*)out, p.L, p.tail, b, d_result, s) !=
+    if (launch_encode((const uint8_t*)in, (uint8_t*)out, p.L, p.tail, b, d_result, s, fast) !=
         hipSuccess)
         return kErrHip;
     if (block_offsets && p.nb &&
@@ -247,6 +247,24 @@ int64_t bshuf_compress_lz4_dev(const void* in, void* out, size_t size, size_t el
             hipSuccess)
         return kErrHip;
     return 0;
+}
+
+int64_t bshuf_compress_lz4_dev(const void* in, void* out, size_t size, size_t elem_size,
+                               size_t block_size, void* ws, size_t ws_bytes, int64_t* d_result,
+                               uint64_t* block_offsets, void* stream) {
+    return compress_dev(in, out, size, elem_size, block_size, ws, ws_bytes, d_result, block_offsets,
+                        stream, false);
+}
+
+// Fast parse v1 (lz4_fast.hip): same framing, workspace and error codes; blocks
+// above 65536 bytes take the exact parse, so such a stream is the exact one.
+int bshuf_lz4_fast_version(void) { return 1; }
+
+int64_t bshuf_compress_lz4_fast_dev(const void* in, void* out, size_t size, size_t elem_size,
+                                    size_t block_size, void* ws, size_t ws_bytes, int64_t* d_result,
+                                    uint64_t* block_offsets, void* stream) {
+    return compress_dev(in, out, size, elem_size, block_size, ws, ws_bytes, d_result, block_offsets,
+                        stream, true);
 }
 
 size_t bshuf_decompress_lz4_dev_workspace(size_t in_nbytes, size_t size, size_t elem_size,
@@ -469,10 +487,10 @@ size_t bshuf_compress_lz4_batch_dev_workspace(const size_t* sizes, size_t count,
     return enc_batch_ws(bp, nullptr, nullptr, nullptr, nullptr);
 }
 
-int64_t bshuf_compress_lz4_batch_dev(const void* const* in, void* const* out, const size_t* sizes,
-                                     size_t count, size_t elem_size, size_t block_size, void* ws,
-                                     size_t ws_bytes, int64_t* d_results, uint64_t* block_offsets,
-                                     void* stream) {
+static int64_t compress_batch(const void* const* in, void* const* out, const size_t* sizes,
+                              size_t count, size_t elem_size, size_t block_size, void* ws,
+                              size_t ws_bytes, int64_t* d_results, uint64_t* block_offsets,
+                              void* stream, bool fast) {
     BatchPlan bp;
     const int64_t r = make_batch(in, out, sizes, nullptr, count, elem_size, block_size, bp);
     if (r) return r;
@@ -486,10 +504,10 @@ int64_t bshuf_compress_lz4_batch_dev(const void* const* in, void* const* out, co
     for (const Seg& g : bp.segs) mixed = mixed || (g.last && ((int64_t)g.last * bp.L.E >= kU16TableLimit) != wide);
     if (mixed) {
         for (size_t i = 0; i < count; i++) {
-            const int64_t e = bshuf_compress_lz4_dev(in[i], out[i], sizes[i], elem_size, block_size,
-                                                     nullptr, 0, d_results + i,
-                                                     block_offsets ? block_offsets + bp.segs[i].first : nullptr,
-                                                     stream);
+            const int64_t e = compress_dev(in[i], out[i], sizes[i], elem_size, block_size, nullptr, 0,
+                                           d_results + i,
+                                           block_offsets ? block_offsets + bp.segs[i].first : nullptr,
+                                           stream, fast);
             if (e) return e;
         }
         return 0;
@@ -504,10 +522,26 @@ int64_t bshuf_compress_lz4_batch_dev(const void* const* in, void* const* out, co
     enc_batch_ws(bp, &b, &dsegs, &blk_seg, (uint8_t*)ws);
     if (stage_upload(bp.segs.data(), count * sizeof(Seg), dsegs, s) != hipSuccess ||
         launch_seg_map(dsegs, (int)count, blk_seg, false, s) != hipSuccess ||
-        launch_encode_batch(dsegs, bp.segs.data(), (int)count, blk_seg, bp.L, b, block_offsets, s) !=
-            hipSuccess)
+        launch_encode_batch(dsegs, bp.segs.data(), (int)count, blk_seg, bp.L, b, block_offsets, s,
+                            fast) != hipSuccess)
         return kErrHip;
     return 0;
+}
+
+int64_t bshuf_compress_lz4_batch_dev(const void* const* in, void* const* out, const size_t* sizes,
+                                     size_t count, size_t elem_size, size_t block_size, void* ws,
+                                     size_t ws_bytes, int64_t* d_results, uint64_t* block_offsets,
+                                     void* stream) {
+    return compress_batch(in, out, sizes, count, elem_size, block_size, ws, ws_bytes, d_results,
+                          block_offsets, stream, false);
+}
+
+int64_t bshuf_compress_lz4_fast_batch_dev(const void* const* in, void* const* out, const size_t* sizes,
+                                          size_t count, size_t elem_size, size_t block_size, void* ws,
+                                          size_t ws_bytes, int64_t* d_results, uint64_t* block_offsets,
+                                          void* stream) {
+    return compress_batch(in, out, sizes, count, elem_size, block_size, ws, ws_bytes, d_results,
+                          block_offsets, stream, true);
 }
 
 size_t bshuf_decompress_lz4_batch_dev_workspace(const size_t* in_nbytes, const size_t* sizes,

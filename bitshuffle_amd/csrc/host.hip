@@ -630,8 +630,8 @@ int64_t bshuf_bitunshuffle(const void* in, void* out, const size_t size, const s
     return transpose_host(in, out, size, elem_size, block_size, false);
 }
 
-int64_t bshuf_compress_lz4(const void* in, void* out, const size_t size, const size_t elem_size,
-                           size_t block_size) {
+static int64_t compress_host(const void* in, void* out, const size_t size, const size_t elem_size,
+                             size_t block_size, bool fast) {
     Plan p;
     const int64_t r = make_plan(size, elem_size, block_size, p);
     if (r) return r;
@@ -648,13 +648,23 @@ int64_t bshuf_compress_lz4(const void* in, void* out, const size_t size, const s
     if (!di || !dout || !ws || !dres) return -1;
     if (!h2d(*c, di, (const uint8_t*)in, 0, bytes)) return fail(*c);
     const bool own = diag_alloc_ws();
-    const int64_t e = bshuf_compress_lz4_dev(di, dout, size, elem_size, block_size, own ? nullptr : ws,
-                                             own ? 0 : wsb, dres, nullptr, c->s);
+    const int64_t e = (fast ? bshuf_compress_lz4_fast_dev : bshuf_compress_lz4_dev)(
+        di, dout, size, elem_size, block_size, own ? nullptr : ws, own ? 0 : wsb, dres, nullptr, c->s);
     if (e < 0) return e;
     int64_t res = 0;
     if (!read_result(*c, dres, res)) return fail(*c);
     if (res > 0 && (size_t)res <= bound && !d2h(*c, (uint8_t*)out, dout, (size_t)res)) return fail(*c);
     return res;
+}
+
+int64_t bshuf_compress_lz4(const void* in, void* out, const size_t size, const size_t elem_size,
+                           size_t block_size) {
+    return compress_host(in, out, size, elem_size, block_size, false);
+}
+
+int64_t bshuf_compress_lz4_fast(const void* in, void* out, const size_t size, const size_t elem_size,
+                                size_t block_size) {
+    return compress_host(in, out, size, elem_size, block_size, true);
 }
 
 int64_t bshuf_decompress_lz4(const void* in, void* out, const size_t size, const size_t elem_size,

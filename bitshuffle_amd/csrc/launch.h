@@ -106,8 +106,12 @@ struct EncodeBufs {
 };
 size_t encode_scan_tmp_bytes(int64_t nblocks);
 int64_t encode_slot_bytes(const Layout& L);
+// fast: the blocks' payloads by the fast parse v1 (lz4_fast.hip) instead of the
+// reference's greedy hash parse, when a block is at most kFastMaxBlockBytes;
+// scratch slots, offset scan, compaction and finish are the same.
+constexpr int64_t kFastMaxBlockBytes = 65536;
 hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64_t tail_bytes,
-                         const EncodeBufs& b, int64_t* d_result, hipStream_t s);
+                         const EncodeBufs& b, int64_t* d_result, hipStream_t s, bool fast = false);
 // Batch of independent streams: segs (device) / hsegs (host copy) describe
 // them, L carries the shared bs and E and L.nfull = total blocks.  Every
 // stream's blocks must use one LZ4 table type (bs * E < 65547, or every
@@ -115,7 +119,7 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
 // header offset inside its own stream.
 hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, const uint32_t* blk_seg,
                                const Layout& L, const EncodeBufs& b, uint64_t* block_offsets,
-                               hipStream_t s);
+                               hipStream_t s, bool fast = false);
 // Largest block (bytes) the LDS-resident encoder accepts.
 int64_t max_device_block_bytes();
 // Blocks above these sizes take the global-memory path (lz4_large.hip).

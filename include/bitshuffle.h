@@ -127,6 +127,31 @@ int64_t bshuf_decompress_lz4_batch_dev_dlen(const void* const* in, const int64_t
                                             size_t block_size, void* ws, size_t ws_bytes,
                                             int64_t* d_results, void* stream);
 
+/* ---- fast encode mode (additive, opt-in): "fast parse v1" ----
+ *
+ * The same framed bitshuffle/LZ4 stream as the entries above -- block
+ * splitting, partial last block, verbatim tail, error codes, workspaces
+ * (bshuf_compress_lz4_dev_workspace / _batch_dev_workspace), output bound
+ * (bshuf_compress_lz4_bound) and stream semantics -- and every bitshuffle/LZ4
+ * reader decodes it, but each block's LZ4 payload comes from a parse that
+ * looks for matches only at the distances 1, 2, 3, 4, 8, P and 2P (P = bytes
+ * per bit plane of the block), not from the reference's hash-table parse: the
+ * bytes differ from the reference encoder's ("fast parse v1").  The
+ * stream is a pure function of (input, elem_size, block_size).  Blocks above
+ * 65536 bytes take the exact parse: such a stream equals the exact one.
+ * bshuf_lz4_fast_version() names the parse rule (1). */
+int bshuf_lz4_fast_version(void);
+int64_t bshuf_compress_lz4_fast(const void* in, void* out, const size_t size,
+                                const size_t elem_size, size_t block_size);
+int64_t bshuf_compress_lz4_fast_dev(const void* in, void* out, size_t size, size_t elem_size,
+                                    size_t block_size, void* ws, size_t ws_bytes,
+                                    int64_t* d_result, uint64_t* block_offsets, void* stream);
+int64_t bshuf_compress_lz4_fast_batch_dev(const void* const* in, void* const* out,
+                                          const size_t* sizes, size_t count, size_t elem_size,
+                                          size_t block_size, void* ws, size_t ws_bytes,
+                                          int64_t* d_results, uint64_t* block_offsets,
+                                          void* stream);
+
 /* Synthetic benchmark inputs of SURVEY.md 8(d), generated on the device
  * (counter based, identical to the CPU definition): gen 0 = int32 ramp,
  * 1 = int16 correlated noise (G1), 2 = float32 smooth field (G2). */
