@@ -41,7 +41,7 @@ size_t enc_ws(const Plan& p, EncodeBufs* b, uint8_t* base) {
     EncodeBufs x;
     x.slot = slot;
     x.scratch = c.take<uint8_t>((size_t)(p.nb * slot));
-    x.foot = c.take<uint64_t>((size_t)(p.nb + 1) * 8);
+    x.foot = c.take<uint64_t>((size_t)(p.nb + 1) * 8 + kEncTicketSets * kTicketSetBytes);
     x.offs = c.take<uint64_t>((size_t)(p.nb + 1) * 8);
     x.scan_tmp_bytes = encode_scan_tmp_bytes(p.nb);
     x.scan_tmp = c.take<void>(x.scan_tmp_bytes);
@@ -69,6 +69,7 @@ size_t dec_ws(const Plan& p, int64_t blocks_end, int64_t in_nbytes, bool need_in
     x.base = c.take<uint64_t>((size_t)(x.nchunks + 1) * 8);
     x.idx_err = c.take<int64_t>(8);
     x.bad = c.take<long long>(8);
+    x.tickets = c.take<uint32_t>(kTicketSetBytes);
     x.scan_tmp_bytes = need_index ? decode_scan_tmp_bytes(x.nchunks) : 0;
     x.scan_tmp = c.take<void>(x.scan_tmp_bytes + 8);
     if ((int64_t)p.L.bs * p.L.E > max_lds_decode_bytes())
@@ -430,7 +431,7 @@ size_t enc_batch_ws(const BatchPlan& bp, EncodeBufs* b, Seg** dsegs, uint32_t** 
     EncodeBufs x;
     x.slot = encode_slot_bytes(bp.L);
     x.scratch = c.take<uint8_t>((size_t)(bp.nb * x.slot));
-    x.foot = c.take<uint64_t>((size_t)(bp.nb + 1) * 8);
+    x.foot = c.take<uint64_t>((size_t)(bp.nb + 1) * 8 + kEncTicketSets * kTicketSetBytes);
     x.offs = c.take<uint64_t>((size_t)(bp.nb + 1) * 8);
     x.scan_tmp_bytes = encode_scan_tmp_bytes(bp.nb);
     x.scan_tmp = c.take<void>(x.scan_tmp_bytes);
@@ -458,6 +459,7 @@ size_t dec_batch_ws(const BatchPlan& bp, DecodeBufs* b, Seg** dsegs, uint32_t** 
     x.base = c.take<uint64_t>((size_t)(bp.nchunks + 1) * 8);
     x.idx_err = c.take<int64_t>(ns * 8);
     x.bad = c.take<long long>(ns * 8);
+    x.tickets = c.take<uint32_t>(kTicketSetBytes);
     x.scan_tmp_bytes = decode_scan_tmp_bytes(bp.nchunks);
     x.scan_tmp = c.take<void>(x.scan_tmp_bytes + 8);
     if (b) *b = x;

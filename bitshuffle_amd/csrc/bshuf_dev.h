@@ -247,4 +247,40 @@ __device__ __forceinline__ void store_group(uint8_t* p, const uint32_t (&w)[2 * 
     }
 }
 
+// Block tickets of a persistent launch (launch.h, "Dynamic block scheduling").
+#ifndef BSHUF_TICKET_SHARDS
+#define BSHUF_TICKET_SHARDS 8  // a power of two; A/B builds: 1 = one counter
+#endif
+constexpr int kTicketShards = BSHUF_TICKET_SHARDS;
+constexpr int kTicketStride = 16;  // u32 words between two shards' counters
+static_assert((kTicketShards & (kTicketShards - 1)) == 0, "shards: a power of two");
+
+// One wave's view of its launch's counters.  request() has lane 0 draw n
+// tickets and does not wait: the first one's number lands in lane 0's register
+// and block() reads it later (a whole parse later in both kernels, so the
+// atomic's round trip is never waited for).  Relaxed and fence-free: only an
+// index travels between workgroups.  ctr == nullptr: the static schedule,
+// block() then steps `last` by the grid size.  (The kernels' files are built
+// with LLVM's atomic optimizer off, Makefile: it would turn the request into a
+// wave reduction that waits for the atomic on the spot.)
+struct Tickets {
+    uint32_t* ctr;  // this workgroup's shard counter
+    int64_t base;   // block of the shard's ticket 0; static: the grid size
+    __device__ __forceinline__ Tickets(uint32_t* set, int64_t first)
+        : ctr(set ? set + (blockIdx.x & (kTicketShards - 1)) * kTicketStride : nullptr),
+          base(set ? first + gridDim.x + (blockIdx.x & (kTicketShards - 1)) : (int64_t)gridDim.x) {}
+    __device__ __forceinline__ uint32_t request(int lane, uint32_t n = 1u) const {
+        uint32_t t = 0;
+        if (ctr && lane == 0) t = __hip_atomic_fetch_add(ctr, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return t;
+    }
+    // the block of requested ticket t (+ k for the k-th of a multiple request);
+    // static: the block one grid behind `last`
+    __device__ __forceinline__ int64_t block(uint32_t t, int64_t last, uint32_t k = 0u) const {
+        if (!ctr) return last + base;
+        const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)t) + k;
+        return base + (int64_t)kTicketShards * (int64_t)v;
+    }
+};
+
 }  // namespace bshuf

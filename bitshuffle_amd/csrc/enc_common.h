@@ -19,6 +19,7 @@ struct EncArgs {
     const uint32_t* blk_seg;
     int32_t raw8;      // EK == 0: every block source is 8-aligned (LDS-staged transpose)
     int64_t blk0;      // batch: global index of this launch's block 0 (pipelined segments)
+    uint32_t* tickets; // this launch's ticket counters (launch.h); nullptr: static schedule
 };
 
 // Registers holding one 8 KiB block for EK-byte elements: 8192 / 64 lanes.

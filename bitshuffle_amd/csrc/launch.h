@@ -25,8 +25,9 @@ class ProfScope {
 };
 
 // Kernel-variant knob for A/B measurements (bshuf_set_variant, per thread,
-// byte-identical variants only); 0 = default.  The kNoPipe bit is not part of
-// the variant (pipe_ctx reads it).
+// byte-identical variants only); 0 = default.  The kNoPipe, kStaticSched and
+// kTicketSched bits are not part of the variant (pipe_ctx / ticket_sched read
+// them).
 int tuning_variant();
 #ifdef BSHUF_DIAG
 int diag_variant();  // timing ablations (wrong output), diag build only
@@ -52,6 +53,30 @@ struct PipeCtx {
 PipeCtx* pipe_ctx(hipStream_t s);
 // s waits for everything enqueued on `from` so far (event ev)
 hipError_t stream_after(hipStream_t s, hipStream_t from, hipEvent_t ev);
+
+// Dynamic block scheduling of the persistent kernels (k_lz4_encode,
+// k_lz4_decode).  A wave's first block is its workgroup index; every later one
+// is drawn from a ticket counter in the call's workspace: shard c = workgroup
+// & (kTicketShards - 1) hands out blocks G + kTicketShards * t + c (G
+// workgroups, ticket t), so a wave whose blocks take longer (their data, a
+// crowded SIMD) takes fewer of them and a launch ends within one block of the
+// last ticket, not with the wave whose fixed share added up to the most time.
+// One set of counters per persistent launch of a call, each on its
+// own 64-byte line; zeroed by stream-ordered work the call does anyway (the
+// encoder's foot[nb] fill, the decoder's token scan).  Only the wave that
+// takes a block changes, never what is written for it.  Which launches draw
+// tickets by default is decided per kernel and block size from measurements
+// (prof.hip, ticket_sched: eight counters hand out about 400 M tickets/s, which
+// the decoder outruns on blocks under 2 KiB); bshuf_set_variant bit
+// kStaticSched: none does, workgroup w takes blocks w, w+G, w+2G, ...; bit
+// kTicketSched: every launch does.
+// (the kernels' side: struct Tickets, bshuf_dev.h)
+constexpr size_t kTicketSetBytes = (size_t)kTicketShards * kTicketStride * sizeof(uint32_t);
+constexpr int kEncTicketSets = kPipeSegs;  // unsegmented encodes use one or two
+constexpr int kStaticSched = 1 << 24;  // static block assignment in both kernels
+constexpr int kTicketSched = 1 << 25;  // tickets in both kernels at every block size
+enum TicketKernel { kTicketsEncode, kTicketsDecode };
+bool ticket_sched(TicketKernel k, int64_t block_bytes);
 
 // Workgroups for a persistent launch: resident blocks per CU (occupancy API,
 // dynamic LDS included) x CUs of the current device, capped by the work.
@@ -97,7 +122,8 @@ hipError_t launch_transpose(const uint8_t* in, uint8_t* out, const Layout& L, bo
 struct EncodeBufs {
     uint8_t* scratch;   // nblocks * slot bytes: [BE32 c][c payload] per block
     int64_t slot;       // bytes per scratch slot (16-aligned, >= 4 + lz4_bound)
-    uint64_t* foot;     // nblocks + 1 u64: 4 + c per block, last = 0
+    uint64_t* foot;     // nblocks + 1 u64: 4 + c per block, last = 0; behind it
+                        // kEncTicketSets sets of ticket counters
     uint64_t* offs;     // nblocks + 1 u64: exclusive scan of foot
     void* scan_tmp;     // hipcub temp storage
     size_t scan_tmp_bytes;
@@ -143,6 +169,7 @@ struct DecodeBufs {
     uint64_t* base;     // nchunks + 1
     int64_t* idx_err;   // 1 word
     long long* bad;     // 1 word: highest failing block index
+    uint32_t* tickets;  // one set of ticket counters (k_lz4_decode)
     void* scan_tmp;
     size_t scan_tmp_bytes;
     int64_t chunk;      // chunk bytes for the index rebuild

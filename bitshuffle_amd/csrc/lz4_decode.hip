@@ -44,6 +44,8 @@ constexpr int kIdxCandCap = 512;   // LDS list of screened candidates (u32 windo
 #ifdef BSHUF_DIAG
 constexpr int kDDiagCopies = 64;
 __device__ unsigned long long g_ddiag[kDDiagCopies * 16];
+// blocks each wave took (its count 3): min, max, sum over waves, waves
+__device__ unsigned long long g_ddiag_bw[4] = {~0ull, 0, 0, 0};
 struct DDiag {
     uint64_t t, acc[8];
     uint32_t cnt[8];
@@ -62,6 +64,12 @@ struct DDiag {
                 atomicAdd(&g_ddiag[(blockIdx.x % kDDiagCopies) * 16 + i], (unsigned long long)acc[i]);
                 atomicAdd(&g_ddiag[(blockIdx.x % kDDiagCopies) * 16 + 8 + i], (unsigned long long)cnt[i]);
             }
+        if (lane == 0) {
+            atomicMin(&g_ddiag_bw[0], (unsigned long long)cnt[3]);
+            atomicMax(&g_ddiag_bw[1], (unsigned long long)cnt[3]);
+            atomicAdd(&g_ddiag_bw[2], (unsigned long long)cnt[3]);
+            atomicAdd(&g_ddiag_bw[3], 1ull);
+        }
     }
 };
 #else
@@ -767,6 +775,8 @@ struct DecArgs {
     int32_t ip_end;     // VAR & 512: the in-place record region ends at this LDS offset
     int64_t blk0, blk1; // k_seq_scan / k_lz4_decode: this launch's blocks [blk0, blk1)
     const int64_t* dlen;  // single stream: length in device memory (in_nbytes = capacity)
+    uint32_t* tickets;    // k_lz4_decode's ticket counters, zeroed by k_seq_scan (launch.h);
+                          // nullptr: static schedule
 };
 
 // The single stream's readable bytes from its device-held length, once per kernel.
@@ -1027,6 +1037,9 @@ struct SeqOut {
 // seq[offs[k]/3 + i] = payload position of sequence i's token (a sequence
 // takes >= 3 record bytes, so the per-block ranges are disjoint).
 __global__ __launch_bounds__(256) void k_seq_scan(DecArgs a, int64_t nb) {
+    // the decode kernel behind this one on the stream starts from zeroed tickets
+    if (a.tickets && blockIdx.x == 0 && threadIdx.x < kTicketShards)
+        a.tickets[threadIdx.x * kTicketStride] = 0;
     const int64_t k = a.blk0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= a.blk1) return;
     resolve_len(a);
@@ -1236,12 +1249,17 @@ __device__ __forceinline__ uint32_t land_record(const PayRegsT<IT>& R, bool in_r
     return sp.loc.seq[sp.o0 / 3 + lane];
 }
 
-// Persistent: workgroup w decodes blocks w, w+G, ...  Software pipeline, per
-// iteration: parse block i; land record i+1 (its loads were issued one whole
-// parse earlier); issue the offsets of i+3 and the record of i+2; store block
-// i.  Every wait on HBM therefore follows a parse, so neither load latency nor
-// the completion of the previous block's stores (gfx9 counts loads and stores
-// on one in-order vmcnt) stalls the wave.
+// Persistent: workgroup w starts with block w and draws every later block from
+// the launch's ticket counters (struct Tickets; a.tickets == nullptr: blocks w,
+// w+G, ...), so a wave whose blocks take longer takes fewer of them and the
+// launch ends within one block of its last ticket.  Software pipeline over
+// the wave's own sequence of blocks, per iteration: parse block i; land record
+// i+1 (its loads were issued one whole parse earlier); issue the offsets of
+// i+3, whose ticket was requested an iteration earlier, request the ticket of
+// i+4, and issue the record of i+2; store block i.  Every wait on HBM
+// therefore follows a parse, so neither load latency, nor the ticket's round
+// trip, nor the completion of the previous block's stores (gfx9 counts loads,
+// returning atomics and stores on one in-order vmcnt) stalls the wave.
 template <int EK, int VAR>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((VAR & 512) ? (EK == 0 ? 4 : 5) : 1)))
 void k_lz4_decode(DecArgs a, int64_t nb) {
@@ -1263,10 +1281,15 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
     auto cbuf_of = [&](const Span& sp) -> lds8* {
         return kIP ? to_lds(smem) + a.ip_end - 16 * span_chunks(a, sp) : Cbuf;
     };
-    const int64_t stride = gridDim.x;
     int64_t blk = a.blk0 + blockIdx.x;
     const int64_t end = a.blk1;  // this launch's blocks [blk0, end); nb: the whole stream(s)
     if (blk >= end) return;
+    // the wave's queue of drawn blocks: blk, next, nn, and in tk the requested
+    // ticket of the block after them.  A shard's tickets only grow, so the
+    // first id >= end ends the queue (every one drawn before it is decoded).
+    const Tickets tks(a.tickets, a.blk0);
+    const uint32_t tk0 = tks.request(lane, 2u);  // next and nn, ahead of the first offsets
+    uint32_t tk = tks.request(lane);
     resolve_len(a);
 
     PayRegsT<kIP ? kPayItersIP : kPayIters> R;
@@ -1281,7 +1304,8 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
         if (in_regs) issue_pay(R, a, cur, lane);
         cur_pos = land_record(R, in_regs, a, cur, cbuf_of(cur), lane);
     }
-    int64_t next = blk + stride;
+    int64_t next = tks.block(tk0, blk);
+    int64_t nn = tks.block(tk0, next, 1u);
     Span nxt = {};
     bool nxt_in_regs = false;
     uint32_t pref_pos = 0;  // kG: token position of block `next`, loaded a parse early
@@ -1298,7 +1322,19 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
         }
     }
     OffRegs O{0, 0};
-    if (next + stride < end) O = issue_offs(a, next + stride, nb, lane);
+    if (nn < end) O = issue_offs(a, nn, nb, lane);
+    // Offsets of the block three ahead (called once nn's have been read out of
+    // O).  Its ticket was requested an iteration ago, in front of that
+    // iteration's loads, which have landed since; the following block's is
+    // requested here, again in front of the loads.
+    int64_t n3 = end;
+    auto offs_ahead = [&]() {
+        n3 = tks.block(tk, nn);
+        if (n3 < end) {
+            tk = tks.request(lane);
+            O = issue_offs(a, n3, nb, lane);
+        }
+    };
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // diagnostic build: 0 fields, 1 literals, 2 matches, 3 inverse transpose
@@ -1341,7 +1377,7 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // the next record replaces this one in LDS; then the loads two ahead
-        const int64_t nn = next + stride;
+        n3 = end;
         Span nxt2 = {};
         bool nxt2_in_regs = false;
         uint32_t nxt_pos = 0;
@@ -1350,7 +1386,7 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
                 nxt_pos = pref_pos;
                 if (nn < end) {
                     nxt2 = span_from(a, O, nb);
-                    if (nn + stride < end) O = issue_offs(a, nn + stride, nb, lane);
+                    offs_ahead();
                     pref_pos = nxt2.loc.seq[nxt2.o0 / 3 + lane];
                     if constexpr (kTouch) t_nxt2 = touch_record(nxt2, lane);
                 }
@@ -1358,7 +1394,7 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
                 nxt_pos = land_record(R, nxt_in_regs, a, nxt, Cbuf, lane);
                 if (nn < end) {
                     nxt2 = span_from(a, O, nb);
-                    if (nn + stride < end) O = issue_offs(a, nn + stride, nb, lane);
+                    offs_ahead();
                     nxt2_in_regs = fits(nxt2);
                     if (nxt2_in_regs) issue_pay(R, a, nxt2, lane);
                 }
@@ -1488,7 +1524,7 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
                 nxt_pos = land_record(R, nxt_in_regs, a, nxt, cbuf_of(nxt), lane);
                 if (nn < end) {
                     nxt2 = span_from(a, O, nb);
-                    if (nn + stride < end) O = issue_offs(a, nn + stride, nb, lane);
+                    offs_ahead();
                     nxt2_in_regs = fits(nxt2);
                     if (nxt2_in_regs) issue_pay(R, a, nxt2, lane);
                 }
@@ -1503,6 +1539,7 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
         cur = nxt;
         cur_pos = nxt_pos;
         next = nn;
+        nn = n3;
         nxt = nxt2;
         nxt_in_regs = nxt2_in_regs;
         if constexpr (kTouch) {
@@ -1871,6 +1908,8 @@ hipError_t decode_impl(DecArgs& a, int64_t nb, bool aligned, hipStream_t s) {
     // 4.20 -> 4.24 ms G1 / 8.00 -> 8.21 ms G2 per 4 GiB, profiles/r04/pipe)
     a.blk0 = 0;
     a.blk1 = nb;
+    // (32-bit tickets number fewer than 2^31 blocks)
+    if (!ticket_sched(kTicketsDecode, (int64_t)L.bs * L.E) || nb >= ((int64_t)1 << 31)) a.tickets = nullptr;
     e = scan_impl(a, nb, s);
     return e != hipSuccess ? e : dec(0, nb, s);
 }
@@ -1916,7 +1955,7 @@ hipError_t launch_decode(const uint8_t* in, int64_t in_nbytes, uint8_t* out, con
         const int64_t nmax = (int64_t)L.bs * L.E;
         DecArgs a{in, in_nbytes, b.offs, out, b.status, b.bad, L, (uint32_t)lz4_bound((int)nmax),
                   (int32_t)((nmax + 15) & ~15), b.seq, nullptr, nullptr,
-                  ((uintptr_t)out & 7) == 0 ? 1 : 0, 0, 0, nb, dlen};
+                  ((uintptr_t)out & 7) == 0 ? 1 : 0, 0, 0, nb, dlen, b.tickets};
         if (nmax > max_lds_decode_bytes()) {
             // large blocks: validated by the same scan (a wave per block),
             // executed in global memory
@@ -1953,7 +1992,7 @@ hipError_t launch_decode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
             al8 = al8 && ((uintptr_t)hsegs[i].out & 7) == 0;
         }
         DecArgs a{nullptr, 0, b.offs, nullptr, b.status, b.bad, L, (uint32_t)lz4_bound((int)nmax),
-                  (int32_t)((nmax + 15) & ~15), b.seq, segs, blk_seg, al8 ? 1 : 0, 0, 0, nb, nullptr};
+                  (int32_t)((nmax + 15) & ~15), b.seq, segs, blk_seg, al8 ? 1 : 0, 0, 0, nb, nullptr, b.tickets};
         e = decode_impl(a, nb, aligned, s);
         if (e != hipSuccess) return e;
     }
@@ -1967,7 +2006,8 @@ hipError_t launch_decode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
 
 #ifdef BSHUF_DIAG
 // Diagnostic build only: read (and reset) k_lz4_decode's phase counters
-// (out[0..7] cycles, out[8..15] counts).
+// (out[0..7] cycles, out[8..15] counts, out[16..19] blocks per wave min / max /
+// sum and the number of waves).
 extern "C" int bshuf_diag_read_dec(unsigned long long* out) {
     static unsigned long long all[bshuf::kDDiagCopies * 16];
     if (hipMemcpyFromSymbol(all, HIP_SYMBOL(bshuf::g_ddiag), sizeof all) != hipSuccess) return -1;
@@ -1975,6 +2015,10 @@ extern "C" int bshuf_diag_read_dec(unsigned long long* out) {
         out[i] = 0;
         for (int c = 0; c < bshuf::kDDiagCopies; c++) out[i] += all[c * 16 + i];
     }
+    static const unsigned long long bw0[4] = {~0ull, 0, 0, 0};
+    if (hipMemcpyFromSymbol(out + 16, HIP_SYMBOL(bshuf::g_ddiag_bw), sizeof bw0) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(bshuf::g_ddiag_bw), bw0, sizeof bw0) != hipSuccess)
+        return -1;
     static const unsigned long long z[bshuf::kDDiagCopies * 16] = {0};
     return hipMemcpyToSymbol(HIP_SYMBOL(bshuf::g_ddiag), z, sizeof z) == hipSuccess ? 0 : -1;
 }

@@ -73,9 +73,13 @@ __device__ unsigned long long g_diag[kDiagCopies * 32];
     } while (0)
 // kernel-level phases of k_lz4_encode (slots 16..19): zero + transpose,
 // parse, emission + copy-out, everything else
+// ... and the blocks each wave took: min, max, sum over waves, waves
+__device__ unsigned long long g_diag_bw[4] = {~0ull, 0, 0, 0};
 #define KDIAG_DECL                                   \
     uint64_t _kt = __builtin_amdgcn_s_memtime();     \
-    uint64_t _kacc[4] = {0, 0, 0, 0};
+    uint64_t _kacc[4] = {0, 0, 0, 0};                \
+    unsigned long long _kblocks = 0;
+#define KBLOCK (++_kblocks)
 #define KSTAMP(i)                                       \
     do {                                                \
         const uint64_t _n = __builtin_amdgcn_s_memtime(); \
@@ -87,9 +91,16 @@ __device__ unsigned long long g_diag[kDiagCopies * 32];
         if (lane == 0)                                                                  \
             for (int _i = 0; _i < 4; _i++)                                              \
                 atomicAdd(&g_diag[(blockIdx.x % kDiagCopies) * 32 + 16 + _i], _kacc[_i]); \
+        if (lane == 0) {                                                                \
+            atomicMin(&g_diag_bw[0], _kblocks);                                         \
+            atomicMax(&g_diag_bw[1], _kblocks);                                         \
+            atomicAdd(&g_diag_bw[2], _kblocks);                                         \
+            atomicAdd(&g_diag_bw[3], 1ull);                                             \
+        }                                                                               \
     } while (0)
 #else
 #define KDIAG_DECL
+#define KBLOCK ((void)0)
 #define KSTAMP(i) ((void)0)
 #define KDIAG_FLUSH ((void)0)
 #define DIAG_DECL
@@ -1878,9 +1889,15 @@ __device__ __forceinline__ void raw_to_lds(const RawRegs& R, lds8* S, int nbytes
 #ifndef BSHUF_FLUSH4
 #define BSHUF_FLUSH4 1  // A/B builds: 0 = round 5's copy-out and zeroing loops
 #endif
-// Persistent: workgroup w handles blocks w, w+G, w+2G, ...  While block k is
-// parsed out of LDS, the 8 KiB of block k+G are already in flight into
-// registers, so HBM latency hides under the (LDS-latency-bound) parse.
+// Persistent: workgroup w starts with block w and draws every later block from
+// its launch's ticket counters (struct Tickets; a.tickets == nullptr: blocks w,
+// w+G, w+2G, ...), so a wave whose blocks take longer takes fewer of them and
+// the launch ends within one block of its last ticket.  While
+// block k is parsed out of LDS, the 8 KiB of the wave's next block are already
+// in flight into registers, so HBM latency hides under the (LDS-latency-bound)
+// parse; that block's ticket was requested one parse before its loads are
+// issued (in front of the previous prefetch, so that it is the oldest entry of
+// the in-order vmcnt by then), the atomic's round trip is never waited for.
 // One wave per workgroup: LDS hand-offs need no s_barrier, and avoiding
 // __syncthreads() keeps its release fence from draining the prefetch.
 template <int EK, bool WIDE, int VAR>
@@ -1893,9 +1910,10 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
     (void)smem;
     lds8* const L0 = lds_origin();
     lds8* D = L0 + kTableBytes;
-    const int64_t stride = gridDim.x;
     int64_t blk = blockIdx.x;
     if (blk >= nb) return;
+    const Tickets tks(a.tickets, 0);
+    uint32_t tk = tks.request(lane);  // the second block's, ahead of the first block's loads
     // block k -> (elements, source): one stream, or a batch of streams
     constexpr bool kBatch = (VAR & 256) != 0;
     auto blk_m = [&](int64_t k) {
@@ -1970,6 +1988,7 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
     KDIAG_DECL
     for (;;) {
         KSTAMP(3);
+        KBLOCK;
         const int m = blk_m(blk);
         const int n = m * E;
         const int P = m / 8;
@@ -2056,6 +2075,13 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
+        // The next block: its ticket is older than the loads the transpose
+        // has just waited for, so reading it waits for nothing -- here, in
+        // front of the record's stores below (behind them the compiler's wait
+        // for the ticket would be a vmcnt(0) that drains them).  The block
+        // after it is requested at once, ahead of the prefetch.
+        const int64_t next = tks.block(tk, blk);
+        if (next < nb) tk = tks.request(lane);
         if constexpr (kDefer) {
             // the previous block's record leaves now, behind this block's
             // transpose: its stores are older than the prefetch below, so the
@@ -2074,7 +2100,6 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
             __builtin_amdgcn_wave_barrier();
         }
         // prefetch the next block while this one is parsed
-        const int64_t next = blk + stride;
         if constexpr (EK != 0) {
             if (next < nb) {
                 const int mn = blk_m(next);
@@ -2486,18 +2511,31 @@ namespace {
 // 11.12 ms with 8 segments, 11.14 with 4; an LDS-free one-wave scan that let
 // the compaction run beside the parse body instead gained only 11.47 -> 11.25 /
 // 11.38 ms.  The scan of segment i reads foot[f_i+1], which segment i+1 may be
-// writing; that element feeds no output of the scan.  foot[nb] = 0 before the
-// fork.  The side stream joins s before `finish` runs on s.
+// writing; that element feeds no output of the scan.  foot[nb] = 0 and the
+// ticket counters behind it (set i for segment i) are zeroed by the caller's
+// fill before the fork.  The side stream joins s before `finish` runs on s.
+// foot[nb] = 0 (the offset scan's last input) and, in the same fill, the
+// call's ticket counters behind it: zero before the first parse launch,
+// whatever the caller's workspace held.
+hipError_t fill_foot_end(const EncodeBufs& b, int64_t nb, hipStream_t s) {
+    return dev_fill(b.foot + nb, 0, sizeof(uint64_t) + kEncTicketSets * kTicketSetBytes, s);
+}
+// Counters of the call's set-th persistent launch (nullptr: static schedule;
+// also above 2^31 blocks, which 32-bit tickets do not number).
+uint32_t* ticket_set(const EncodeBufs& b, const Layout& L, int64_t nb, int set) {
+    if (!ticket_sched(kTicketsEncode, (int64_t)L.bs * L.E) || nb >= ((int64_t)1 << 31)) return nullptr;
+    return reinterpret_cast<uint32_t*>(b.foot + nb + 1) + (size_t)set * (kTicketSetBytes / sizeof(uint32_t));
+}
+
 template <class Enc, class Fin>
 hipError_t encode_pipelined(int64_t nb, hipStream_t s, PipeCtx* pc, const EncodeBufs& b, Enc enc,
                             uint8_t* out, const Seg* segs, const uint32_t* blk_seg,
                             uint64_t* block_offsets, Fin finish) {
-    hipError_t e = dev_fill(b.foot + nb, 0, sizeof(uint64_t), s);
-    if (e == hipSuccess) e = stream_after(pc->side, s, pc->ev[0]);
+    hipError_t e = stream_after(pc->side, s, pc->ev[0]);
     for (int i = 0; i < kPipeSegs && e == hipSuccess; i++) {
         const int64_t f0 = nb * i / kPipeSegs, f1 = nb * (i + 1) / kPipeSegs;
         if (f1 == f0) continue;
-        e = enc(f0, f1);
+        e = enc(f0, f1, i);
         if (e == hipSuccess) e = stream_after(pc->side, s, pc->ev[1 + i]);
         if (e != hipSuccess) break;
         {
@@ -2546,7 +2584,8 @@ size_t encode_scan_tmp_bytes(int64_t nblocks) {
 hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64_t tail_bytes,
                          const EncodeBufs& b, int64_t* d_result, hipStream_t s, bool fast) {
     const int64_t nb = L.nblocks();
-    hipError_t e;
+    hipError_t e = fill_foot_end(b, nb, s);
+    if (e != hipSuccess) return e;
     // fast parse v1 covers blocks up to kFastMaxBlockBytes; above, the exact path
     fast = fast && (int64_t)L.bs * L.E <= kFastMaxBlockBytes;
     if (nb > 0 && (int64_t)L.bs * L.E > max_lds_encode_bytes()) {
@@ -2567,9 +2606,10 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
         const bool wide_last = L.last && (int64_t)L.last * L.E >= kU16TableLimit;
         const bool aligned = ((uintptr_t)in & 15) == 0;
         const int ek = aligned && (L.E == 1 || L.E == 2 || L.E == 4 || L.E == 8) ? L.E : 0;
-        auto go = [&](Layout LL, bool w, int64_t count, int64_t first) -> hipError_t {
+        auto go = [&](Layout LL, bool w, int64_t count, int64_t first, int set) -> hipError_t {
             EncArgs aa = a;
             aa.L = LL;
+            aa.tickets = ticket_set(b, L, nb, set);
             // shift the base so blockIdx 0 is block `first`
             aa.in = a.in + first * (int64_t)L.bs * L.E;
             aa.scratch = a.scratch + first * b.slot;
@@ -2591,8 +2631,8 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
             return hipErrorInvalidValue;
         };
         PipeCtx* pc = (wide == wide_last || !L.last) && nb >= kPipeMinBlocks ? pipe_ctx(s) : nullptr;
-        if (pc) return encode_pipelined(nb, s, pc, b, [&](int64_t f0, int64_t f1) {
-            return go(L, wide, f1 - f0, f0);
+        if (pc) return encode_pipelined(nb, s, pc, b, [&](int64_t f0, int64_t f1, int set) {
+            return go(L, wide, f1 - f0, f0, set);
         }, out, nullptr, nullptr, nullptr, [&](hipStream_t st) {
             const uint8_t* tail_src = in + (L.nfull * (int64_t)L.bs + L.last) * L.E;
             ProfScope prof("k_encode_finish", st);
@@ -2601,17 +2641,15 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
             return hipGetLastError();
         });
         if (wide == wide_last || !L.last) {
-            e = go(L, wide, nb, 0);
+            e = go(L, wide, nb, 0, 0);
         } else {
             Layout Lf = L;
             Lf.last = 0;
-            e = go(Lf, wide, L.nfull, 0);
-            if (e == hipSuccess) e = go(L, wide_last, 1, L.nfull);
+            e = go(Lf, wide, L.nfull, 0, 0);
+            if (e == hipSuccess) e = go(L, wide_last, 1, L.nfull, 1);
         }
         if (e != hipSuccess) return e;
     }
-    e = dev_fill(b.foot + nb, 0, sizeof(uint64_t), s);
-    if (e != hipSuccess) return e;
     size_t tmp = b.scan_tmp_bytes;
     {
         ProfScope prof("scan_block_offsets", s);
@@ -2637,7 +2675,8 @@ hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
                                const Layout& L, const EncodeBufs& b, uint64_t* block_offsets,
                                hipStream_t s, bool fast) {
     const int64_t nb = L.nfull;  // total blocks of the batch
-    hipError_t e;
+    hipError_t e = fill_foot_end(b, nb, s);
+    if (e != hipSuccess) return e;
     fast = fast && (int64_t)L.bs * L.E <= kFastMaxBlockBytes;
     if (nb > 0) {
         const int64_t nmax = (int64_t)L.bs * L.E;
@@ -2657,8 +2696,9 @@ hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
         const int ek = aligned && (L.E == 1 || L.E == 2 || L.E == 4 || L.E == 8) ? L.E : 0;
         // blocks [f0, f1) of the batch: the segment table is indexed globally
         // (blk0), scratch slots and sizes relative to f0
-        auto go = [&](int64_t f0, int64_t f1) -> hipError_t {
+        auto go = [&](int64_t f0, int64_t f1, int set) -> hipError_t {
             EncArgs aa = a;
+            aa.tickets = ticket_set(b, L, nb, set);
             aa.blk0 = f0;
             aa.scratch = a.scratch + f0 * b.slot;
             aa.foot = a.foot + f0;
@@ -2686,11 +2726,9 @@ hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
                                L.bs, L.E);
             return hipGetLastError();
         });
-        e = go(0, nb);
+        e = go(0, nb, 0);
         if (e != hipSuccess) return e;
     }
-    e = dev_fill(b.foot + nb, 0, sizeof(uint64_t), s);
-    if (e != hipSuccess) return e;
     size_t tmp = b.scan_tmp_bytes;
     {
         ProfScope prof("scan_block_offsets", s);
@@ -2737,6 +2775,11 @@ extern "C" int bshuf_diag_read(unsigned long long* out) {
         out[i] = 0;
         for (int c = 0; c < bshuf::kDiagCopies; c++) out[i] += all[c * 32 + i];
     }
+    // out[20..23]: blocks per wave min / max / sum, waves (all launches since the last read)
+    static const unsigned long long bw0[4] = {~0ull, 0, 0, 0};
+    if (hipMemcpyFromSymbol(out + 20, HIP_SYMBOL(bshuf::g_diag_bw), sizeof bw0) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(bshuf::g_diag_bw), bw0, sizeof bw0) != hipSuccess)
+        return -1;
     static const unsigned long long z[bshuf::kDiagCopies * 32] = {0};
     return hipMemcpyToSymbol(HIP_SYMBOL(bshuf::g_diag), z, sizeof z) == hipSuccess ? 0 : -1;
 }

@@ -59,7 +59,19 @@ bool prof_on() { return P().on; }
 // A/B knob: per calling thread, and only byte-identical variants are accepted
 // (the timing ablations that change the output exist in the diag build only).
 static thread_local int t_variant = 0;
-int tuning_variant() { return t_variant & ~kNoPipe; }
+int tuning_variant() { return t_variant & ~(kNoPipe | kStaticSched | kTicketSched); }
+// Dynamic block scheduling per kernel and block size (launch.h; the numbers:
+// DESIGN.md 6.5, profiles/dyn_sched).  4 GiB G1 per launch, static -> tickets:
+// k_lz4_encode 1.147 -> 1.093 ms, k_lz4_decode 3.10 -> 2.56 ms.  The encoder
+// gains at every block size measured (128 B: 0.951 -> 0.723 ms).  The decoder
+// gets through small blocks faster than eight counters hand them out: 2 KiB
+// blocks 1.405 -> 1.355 ms, 1 KiB 2.22 -> 2.73, 128 B 3.39 -> 5.25.
+constexpr int64_t kDecodeTicketMinBlock = 2048;
+bool ticket_sched(TicketKernel k, int64_t block_bytes) {
+    if (t_variant & kStaticSched) return false;
+    if (t_variant & kTicketSched) return true;
+    return k == kTicketsEncode || block_bytes >= kDecodeTicketMinBlock;
+}
 
 namespace {
 // The calling thread's side streams, one per device (kept for the thread's
@@ -193,8 +205,10 @@ int bshuf_set_variant(int v) {
     // (search_entry), 2793472 / 3072000 (the defaults) those with the whole
     // parse loop as one asm block (parse_chain) and the emission's literal
     // runs by lane_runs; any of
-    // them | kNoPipe (1 << 20): no pipelined encode (launch.h)
-    const int vv = v & ~kNoPipe;
+    // them | kNoPipe (1 << 20): no pipelined encode, | kStaticSched (1 << 24) /
+    // kTicketSched (1 << 25): static / ticket block assignment in both
+    // persistent kernels (launch.h)
+    const int vv = v & ~(kNoPipe | kStaticSched | kTicketSched);
     if (vv != 0 && vv != 2 && vv != 4 && vv != 8 && vv != 16 && vv != 32 && vv != 64 && vv != 128 && vv != 512 && vv != 1024 && vv != 2048 && vv != 4096 && vv != 8192 && vv != 16384 && vv != 24576 && vv != 40960 && vv != 57344 && vv != 65536 && vv != 319488 &&
         vv != 172032 && vv != 450560 &&
         vv != 2793472 && vv != 3072000)

@@ -3,6 +3,8 @@ timing only): 0 full, 8 no inverse transpose/stores, 64 no sequence
 execution, 72 neither, 1024 no literal copies, 2048 no match copies; then
 k_lz4_decode's s_memtime phase split of a full decode (cycles per block,
 summed over waves; the clock reads themselves add a little to every phase).
+Last line: the blocks each wave took (equal under the static schedule,
+variant 16777216; spread under tickets).
 Usage: python tools/diag_decode.py [GiB] [gen] [variant]"""
 import ctypes
 import os
@@ -42,7 +44,7 @@ abl(0)
 
 rd = B.lib.bshuf_diag_read_dec
 rd.argtypes = [ctypes.POINTER(ctypes.c_ulonglong)]
-buf = (ctypes.c_ulonglong * 16)()
+buf = (ctypes.c_ulonglong * 20)()
 rd(buf)
 y, r = api.decompress_lz4_dev(c, x.shape, x.dtype, sync=False)
 torch.cuda.synchronize()
@@ -54,3 +56,5 @@ for i, nm in enumerate(names):
     print("%-18s %8d cyc/block %5.1f%%" % (nm, buf[i] // blocks, 100.0 * buf[i] / max(1, tot)))
 print("blocks %d  sequences/block %.1f  batches/block %.1f  coop matches/block %.1f" % (
     blocks, buf[8] / blocks, buf[9] / blocks, buf[10] / blocks))
+print("blocks per wave: min %d  max %d  mean %.2f  (%d waves)" % (
+    buf[16], buf[17], buf[18] / max(buf[19], 1), buf[19]))

@@ -1,5 +1,6 @@
 """Phase split of k_lz4_encode from the diagnostic build (BSHUF_DIAG stamps).
-Usage: python tools/diag_encode.py [GiB] [gen] [elem_size]   (runs on the GPU box)"""
+Usage: python tools/diag_encode.py [GiB] [gen] [elem_size] [variant]   (runs on the GPU box;
+variant 16777216 = static block assignment)"""
 import ctypes
 import os
 import sys
@@ -19,6 +20,8 @@ x = torch.empty(n, dtype=torch.int16 if gen == 1 else torch.float32, device="cud
 B.synth_fill_dev(x, gen)
 if es:
     x = x.view(torch.uint8)[: (x.numel() * x.element_size() // es) * es]
+if len(sys.argv) > 4:
+    assert B.lib.bshuf_set_variant(int(sys.argv[4])) == 0
 rd = B.lib.bshuf_diag_read
 rd.argtypes = [ctypes.c_void_p]
 buf = (ctypes.c_ulonglong * 32)()
@@ -47,4 +50,7 @@ for i, nm in enumerate(kn):
     print("kernel %-15s %8.0f cyc/block  %5.1f%%" % (nm, v[16 + i] / blocks, 100.0 * v[16 + i] / max(ktot, 1)))
 for i, nm in enumerate(cnt):
     print("%-18s %8.2f per block" % (nm, v[8 + i] / blocks))
+# blocks per wave over the call's parse launches: equal under the static
+# schedule, spread under tickets (waves that share a SIMD take fewer)
+print("blocks per wave: min %d  max %d  mean %.2f  (%d waves)" % (v[20], v[21], v[22] / max(v[23], 1), v[23]))
 print("kernel ms", {k: round(t / c_, 3) for k, (c_, t) in prof.items()})
