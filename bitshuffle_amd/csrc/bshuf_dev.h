@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ticket_steal.h"
+
 namespace bshuf {
 
 constexpr int kWave = 64;
@@ -247,40 +249,191 @@ __device__ __forceinline__ void store_group(uint8_t* p, const uint32_t (&w)[2 * 
     }
 }
 
-// Block tickets of a persistent launch (launch.h, "Dynamic block scheduling").
-#ifndef BSHUF_TICKET_SHARDS
-#define BSHUF_TICKET_SHARDS 8  // a power of two; A/B builds: 1 = one counter
-#endif
-constexpr int kTicketShards = BSHUF_TICKET_SHARDS;
+// Block tickets of a persistent launch (launch.h, "Dynamic block scheduling";
+// kTicketShards and the stealing arithmetic: ticket_steal.h).
 constexpr int kTicketStride = 16;  // u32 words between two shards' counters
-static_assert((kTicketShards & (kTicketShards - 1)) == 0, "shards: a power of two");
+// Counter headroom.  A shard's counter ends at its limit (<= nb / kTicketShards
+// + 1) plus what the waves over-draw: each at most its pipeline depth (three
+// pending tickets in the decoder) plus kTicketShards failed steals.
+constexpr int64_t kTicketMaxWaves = 4608;  // 256 CUs x 18 resident waves
+constexpr int64_t kTicketOverdraw = kTicketMaxWaves * (3 + kTicketShards);
+static_assert(((int64_t)1 << 31) / kTicketShards + 1 + kTicketOverdraw < ((int64_t)1 << 32),
+              "32-bit counters cover every nb < 2^31");
+
+// A requested ticket: its number (lane 0's register, in flight until read) and
+// the shard it was drawn from (wave-uniform: an SGPR).
+struct Ticket {
+    uint32_t t;
+    int shard;
+};
 
 // One wave's view of its launch's counters.  request() has lane 0 draw n
-// tickets and does not wait: the first one's number lands in lane 0's register
-// and block() reads it later (a whole parse later in both kernels, so the
-// atomic's round trip is never waited for).  Relaxed and fence-free: only an
-// index travels between workgroups.  ctr == nullptr: the static schedule,
-// block() then steps `last` by the grid size.  (The kernels' files are built
-// with LLVM's atomic optimizer off, Makefile: it would turn the request into a
-// wave reduction that waits for the atomic on the spot.)
-struct Tickets {
-    uint32_t* ctr;  // this workgroup's shard counter
-    int64_t base;   // block of the shard's ticket 0; static: the grid size
-    __device__ __forceinline__ Tickets(uint32_t* set, int64_t first)
-        : ctr(set ? set + (blockIdx.x & (kTicketShards - 1)) * kTicketStride : nullptr),
-          base(set ? first + gridDim.x + (blockIdx.x & (kTicketShards - 1)) : (int64_t)gridDim.x) {}
-    __device__ __forceinline__ uint32_t request(int lane, uint32_t n = 1u) const {
+// tickets of the wave's shard and does not wait: the first one's number lands
+// in lane 0's register and block() reads it later (a whole parse later in both
+// kernels, so the atomic's round trip is never waited for).  Relaxed and
+// fence-free: only an index travels between workgroups.  set == nullptr: the
+// static schedule, block() then steps `last` by the grid size.  (The kernels'
+// files are built with LLVM's atomic optimizer off, Makefile: it would turn the
+// request into a wave reduction that waits for the atomic on the spot.)
+//
+// Stealing.  A wave starts in shard blockIdx.x & (kTicketShards - 1).  The
+// first time a ticket names a block >= end, block() looks at all the launch's
+// counters (one load by lanes 0..kTicketShards-1), picks the shard with the
+// most tickets left (ticket_victim), draws one ticket there and waits for it --
+// the only waited-for atomic, and only at the end of a launch.  A valid block
+// makes that shard the wave's own: later requests go there, non-waiting as
+// before.  Three invariants:
+//  * The steal loop is bounded by construction.  Counters only grow, so a
+//    failed draw proves that shard empty for good (`dead`, never chosen
+//    again); at most kTicketShards iterations and as many failed draws in a
+//    wave's life, no spin, no wait on another wave.  A wave that finds
+//    nothing leaves.
+//  * A ticket requested before a switch belongs to the old shard (the encoder
+//    holds one, a deeper queue like the decoder's up to three: tk0 for two
+//    blocks, and tk); the new
+//    shard's base would turn it into a block nobody drew.  Every Ticket
+//    carries its shard, and one of a shard that is not the wave's current one
+//    counts as exhausted (and is replaced by a steal).  A wave leaves a shard
+//    only when that shard ran out, or with no ticket of it pending (both
+//    kernels read every pending ticket before they request again), and a
+//    shard that ran out stays out, so nothing valid is ever dropped.
+//  * block() returns a valid block or `end`, never a gap: a queue of drawn
+//    blocks like the decoder's (blk, next, nn, n3) keeps its rule that the
+//    first id >= end ends it.  `end` is the launch's last block + 1 (with a
+//    device-held length: the capacity's; blocks behind the real end are drawn
+//    and dropped as before).
+// STEAL = false compiles the stealing out (no shard tags, no `dead`, block()
+// as before it existed): k_lz4_decode, which measured slower with it
+// (profiles/ticket_steal/README.md).
+template <bool STEAL>
+struct TicketsT {
+    uint32_t* set;  // the launch's counters; nullptr: static schedule
+    int64_t g0;     // block of shard 0's ticket 0; static: the grid size
+    int64_t end;    // the launch's blocks end here
+    int shard;      // the shard this wave draws from
+    uint32_t dead;  // shards a waited-for draw of this wave found empty (a bit each)
+    bool steal;
+    __device__ __forceinline__ TicketsT(uint32_t* s, int64_t first, int64_t e, bool st)
+        : set(s),
+          g0(s ? first + gridDim.x : (int64_t)gridDim.x),
+          end(e),
+          shard((int)(blockIdx.x & (kTicketShards - 1))),
+          dead(0u),
+          steal(STEAL && st && kTicketShards > 1) {}
+    __device__ __forceinline__ Ticket request(int lane, uint32_t n = 1u) const {
         uint32_t t = 0;
-        if (ctr && lane == 0) t = __hip_atomic_fetch_add(ctr, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return t;
+        if (set && lane == 0)
+            t = __hip_atomic_fetch_add(set + shard * kTicketStride, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return Ticket{t, shard};
     }
-    // the block of requested ticket t (+ k for the k-th of a multiple request);
-    // static: the block one grid behind `last`
-    __device__ __forceinline__ int64_t block(uint32_t t, int64_t last, uint32_t k = 0u) const {
-        if (!ctr) return last + base;
-        const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)t) + k;
-        return base + (int64_t)kTicketShards * (int64_t)v;
+    // the block of requested ticket q (+ k for the k-th of a multiple request),
+    // or one stolen in its place, or a value >= end: nothing is left; static:
+    // the block one grid behind `last`
+    // (shard numbers and blocks go through readfirstlane wherever they are
+    // made: wave-uniform by construction, and the kernels need them in SGPRs)
+    __device__ __forceinline__ int64_t block(const Ticket& q, int64_t last, uint32_t k = 0u) {
+        if (!set) return last + g0;
+        if constexpr (!STEAL) {
+            const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.t) + k;
+            return g0 + shard + (int64_t)kTicketShards * (int64_t)v;
+        }
+        if (__builtin_amdgcn_readfirstlane(q.shard) == shard) {
+            const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.t) + k;
+            const int64_t b = g0 + shard + (int64_t)kTicketShards * (int64_t)v;
+            if (b < end || !steal) return b;
+        }
+        return uni64(steal_block());
+    }
+    static __device__ __forceinline__ int64_t uni64(int64_t x) {
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+        return (int64_t)(((uint64_t)hi << 32) | lo);
+    }
+    __device__ __forceinline__ int64_t steal_block() {
+        const int lane = threadIdx.x;  // one wave per workgroup
+#pragma unroll 1
+        for (int i = 0; i < kTicketShards; i++) {
+            // peek: relaxed, agent scope (served by L2, not the CU's L1)
+            uint32_t left = 0;
+            if (lane < kTicketShards) {
+                const uint32_t drawn =
+                    __hip_atomic_load(set + lane * kTicketStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                left = ticket_remaining(ticket_limit(g0, 0, end, lane), drawn);
+            }
+            uint32_t rem[kTicketShards];
+#pragma unroll
+            for (int c = 0; c < kTicketShards; c++)
+                rem[c] = (dead >> c) & 1u ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)left, c);
+            const int victim = __builtin_amdgcn_readfirstlane(ticket_victim(rem, shard));
+            if (victim < 0) break;
+            // draw, and wait for it
+            uint32_t t = 0;
+            if (lane == 0)
+                t = __hip_atomic_fetch_add(set + victim * kTicketStride, 1u, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+            const int64_t b = g0 + victim + (int64_t)kTicketShards * (int64_t)v;
+            if (b < end) {
+                shard = victim;  // (a readfirstlane's result)
+                return b;
+            }
+            dead |= 1u << victim;  // another thief emptied it in between
+        }
+        return end;
     }
 };
+
+using Tickets = TicketsT<true>;
+
+// Diagnostic build only (-DBSHUF_DIAG, tools/diag_encode.py / diag_decode.py):
+// when each ticket shard's waves start and leave, and whose blocks they took.
+// Per launch slot and home shard, kShardDiagWords words: earliest start of a
+// wave's first block, latest exit, blocks taken from the home shard, blocks
+// taken from others, waves that took any from others.  The clock is
+// s_memrealtime (100 MHz, one counter for the device): the shards sit on
+// different XCDs, whose s_memtime counters need not agree.
+#ifdef BSHUF_DIAG
+constexpr int kShardDiagSlots = 16;  // launches kept since the last read (round robin)
+constexpr int kShardDiagWords = 5;
+constexpr int kShardDiagSize = kShardDiagSlots * kTicketShards * kShardDiagWords;
+struct ShardDiag {
+    uint64_t t0;
+    uint32_t own = 1, stolen = 0;  // the first block comes with the workgroup index
+    int home;
+    __device__ __forceinline__ ShardDiag()
+        : t0(__builtin_amdgcn_s_memrealtime()), home((int)(blockIdx.x & (kTicketShards - 1))) {}
+    // a block was drawn (b < t.end), from the shard that is now the wave's
+    template <bool STEAL>
+    __device__ __forceinline__ void drew(const TicketsT<STEAL>& t, int64_t b) {
+        if (b >= t.end) return;
+        if (t.shard == home) own++;
+        else stolen++;
+    }
+    __device__ __forceinline__ void flush(unsigned long long* g, int slot, int lane) const {
+        if (lane != 0) return;
+        unsigned long long* p = g + ((slot % kShardDiagSlots) * kTicketShards + home) * kShardDiagWords;
+        atomicMin(p + 0, (unsigned long long)t0);
+        atomicMax(p + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+        atomicAdd(p + 2, (unsigned long long)own);
+        atomicAdd(p + 3, (unsigned long long)stolen);
+        atomicAdd(p + 4, stolen ? 1ull : 0ull);
+    }
+};
+// host side of a read: copy out and reset (the minimum's words to all ones)
+template <class Sym>
+inline int shard_diag_read(const Sym& sym, unsigned long long* out) {
+    static unsigned long long init[kShardDiagSize];
+    if (hipMemcpyFromSymbol(out, sym, sizeof init) != hipSuccess) return -1;
+    for (int i = 0; i < kShardDiagSize; i++) init[i] = i % kShardDiagWords == 0 ? ~0ull : 0ull;
+    return hipMemcpyToSymbol(sym, init, sizeof init) == hipSuccess ? 0 : -1;
+}
+#define SHARD_DIAG_DECL ShardDiag _sd
+#define SHARD_DIAG_DREW(t, b) _sd.drew(t, b)
+#define SHARD_DIAG_FLUSH(g, slot, lane) _sd.flush(g, slot, lane)
+#else
+#define SHARD_DIAG_DECL ((void)0)
+#define SHARD_DIAG_DREW(t, b) ((void)0)
+#define SHARD_DIAG_FLUSH(g, slot, lane) ((void)0)
+#endif
 
 }  // namespace bshuf

@@ -20,6 +20,10 @@ struct EncArgs {
     int32_t raw8;      // EK == 0: every block source is 8-aligned (LDS-staged transpose)
     int64_t blk0;      // batch: global index of this launch's block 0 (pipelined segments)
     uint32_t* tickets; // this launch's ticket counters (launch.h); nullptr: static schedule
+    int32_t steal;     // a wave whose ticket shard has run out draws from the others
+#ifdef BSHUF_DIAG
+    int32_t diag_slot; // this launch's slot of the per-shard finish table
+#endif
 };
 
 // Registers holding one 8 KiB block for EK-byte elements: 8192 / 64 lanes.

@@ -25,9 +25,9 @@ class ProfScope {
 };
 
 // Kernel-variant knob for A/B measurements (bshuf_set_variant, per thread,
-// byte-identical variants only); 0 = default.  The kNoPipe, kStaticSched and
-// kTicketSched bits are not part of the variant (pipe_ctx / ticket_sched read
-// them).
+// byte-identical variants only); 0 = default.  The kNoPipe, kStaticSched,
+// kTicketSched and kNoSteal bits are not part of the variant (pipe_ctx /
+// ticket_sched / ticket_steal read them).
 int tuning_variant();
 #ifdef BSHUF_DIAG
 int diag_variant();  // timing ablations (wrong output), diag build only
@@ -61,6 +61,13 @@ hipError_t stream_after(hipStream_t s, hipStream_t from, hipEvent_t ev);
 // workgroups, ticket t), so a wave whose blocks take longer (their data, a
 // crowded SIMD) takes fewer of them and a launch ends within one block of the
 // last ticket, not with the wave whose fixed share added up to the most time.
+// A shard covers a fixed eighth of the blocks, so an encoder wave whose shard
+// has run out steals (blocks of 1 KiB and more; the decoder and smaller blocks
+// measured slower with it, prof.hip ticket_steal): it looks at the launch's
+// counters, draws (and waits for) one ticket of the shard with the most left
+// and goes on there, until every shard is empty (ticket_steal.h; the
+// invariants: struct Tickets).  Only the end of a launch pays for that;
+// counters over-draw by at most 3 + kTicketShards per wave.
 // One set of counters per persistent launch of a call, each on its
 // own 64-byte line; zeroed by stream-ordered work the call does anyway (the
 // encoder's foot[nb] fill, the decoder's token scan).  Only the wave that
@@ -69,14 +76,17 @@ hipError_t stream_after(hipStream_t s, hipStream_t from, hipEvent_t ev);
 // (prof.hip, ticket_sched: eight counters hand out about 400 M tickets/s, which
 // the decoder outruns on blocks under 2 KiB); bshuf_set_variant bit
 // kStaticSched: none does, workgroup w takes blocks w, w+G, w+2G, ...; bit
-// kTicketSched: every launch does.
+// kTicketSched: every launch does, and steals; bit kNoSteal: a wave leaves
+// when its own shard runs out.
 // (the kernels' side: struct Tickets, bshuf_dev.h)
 constexpr size_t kTicketSetBytes = (size_t)kTicketShards * kTicketStride * sizeof(uint32_t);
 constexpr int kEncTicketSets = kPipeSegs;  // unsegmented encodes use one or two
 constexpr int kStaticSched = 1 << 24;  // static block assignment in both kernels
 constexpr int kTicketSched = 1 << 25;  // tickets in both kernels at every block size
+constexpr int kNoSteal = 1 << 26;      // no stealing between ticket shards
 enum TicketKernel { kTicketsEncode, kTicketsDecode };
 bool ticket_sched(TicketKernel k, int64_t block_bytes);
+bool ticket_steal(int64_t block_bytes);  // k_lz4_encode only
 
 // Workgroups for a persistent launch: resident blocks per CU (occupancy API,
 // dynamic LDS included) x CUs of the current device, capped by the work.

@@ -46,6 +46,9 @@ constexpr int kDDiagCopies = 64;
 __device__ unsigned long long g_ddiag[kDDiagCopies * 16];
 // blocks each wave took (its count 3): min, max, sum over waves, waves
 __device__ unsigned long long g_ddiag_bw[4] = {~0ull, 0, 0, 0};
+// ... and per launch and ticket shard: start, exit, own / stolen blocks (ShardDiag)
+__device__ unsigned long long g_ddiag_shard[kShardDiagSize];
+int g_ddiag_launches = 0;
 struct DDiag {
     uint64_t t, acc[8];
     uint32_t cnt[8];
@@ -777,6 +780,9 @@ struct DecArgs {
     const int64_t* dlen;  // single stream: length in device memory (in_nbytes = capacity)
     uint32_t* tickets;    // k_lz4_decode's ticket counters, zeroed by k_seq_scan (launch.h);
                           // nullptr: static schedule
+#ifdef BSHUF_DIAG
+    int32_t diag_slot;    // this launch's slot of the per-shard finish table
+#endif
 };
 
 // The single stream's readable bytes from its device-held length, once per kernel.
@@ -1287,9 +1293,11 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
     // the wave's queue of drawn blocks: blk, next, nn, and in tk the requested
     // ticket of the block after them.  A shard's tickets only grow, so the
     // first id >= end ends the queue (every one drawn before it is decoded).
-    const Tickets tks(a.tickets, a.blk0);
-    const uint32_t tk0 = tks.request(lane, 2u);  // next and nn, ahead of the first offsets
-    uint32_t tk = tks.request(lane);
+    // (no stealing between the shards here: it measured slower, bshuf_dev.h)
+    TicketsT<false> tks(a.tickets, a.blk0, end, false);
+    const Ticket tk0 = tks.request(lane, 2u);  // next and nn, ahead of the first offsets
+    Ticket tk = tks.request(lane);
+    SHARD_DIAG_DECL;
     resolve_len(a);
 
     PayRegsT<kIP ? kPayItersIP : kPayIters> R;
@@ -1305,7 +1313,9 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
         cur_pos = land_record(R, in_regs, a, cur, cbuf_of(cur), lane);
     }
     int64_t next = tks.block(tk0, blk);
+    SHARD_DIAG_DREW(tks, next);
     int64_t nn = tks.block(tk0, next, 1u);
+    SHARD_DIAG_DREW(tks, nn);
     Span nxt = {};
     bool nxt_in_regs = false;
     uint32_t pref_pos = 0;  // kG: token position of block `next`, loaded a parse early
@@ -1330,6 +1340,7 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
     int64_t n3 = end;
     auto offs_ahead = [&]() {
         n3 = tks.block(tk, nn);
+        SHARD_DIAG_DREW(tks, n3);
         if (n3 < end) {
             tk = tks.request(lane);
             O = issue_offs(a, n3, nb, lane);
@@ -1548,6 +1559,7 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
         }
     }
     dg.flush(lane);
+    SHARD_DIAG_FLUSH(g_ddiag_shard, a.diag_slot, lane);
 }
 
 // Result: bytes consumed, or the error of the LAST failing block (the
@@ -1897,6 +1909,9 @@ hipError_t decode_impl(DecArgs& a, int64_t nb, bool aligned, hipStream_t s) {
         DecArgs aa = a;
         aa.blk0 = f0;
         aa.blk1 = f1;
+#ifdef BSHUF_DIAG
+        aa.diag_slot = g_ddiag_launches++;
+#endif
         const dim3 grid((unsigned)persistent_grid(fn, kWave, lds, f1 - f0));
         ProfScope prof("k_lz4_decode", st);
         void* args[] = {&aa, const_cast<int64_t*>(&nb)};
@@ -2021,5 +2036,12 @@ extern "C" int bshuf_diag_read_dec(unsigned long long* out) {
         return -1;
     static const unsigned long long z[bshuf::kDDiagCopies * 16] = {0};
     return hipMemcpyToSymbol(HIP_SYMBOL(bshuf::g_ddiag), z, sizeof z) == hipSuccess ? 0 : -1;
+}
+// k_lz4_decode's per-shard table of the launches since the last read (ShardDiag,
+// bshuf_dev.h: kShardDiagSize words); returns their number, and resets.
+extern "C" int bshuf_diag_read_shards_dec(unsigned long long* out) {
+    const int n = bshuf::g_ddiag_launches;
+    bshuf::g_ddiag_launches = 0;
+    return bshuf::shard_diag_read(HIP_SYMBOL(bshuf::g_ddiag_shard), out) == 0 ? n : -1;
 }
 #endif

@@ -75,6 +75,9 @@ __device__ unsigned long long g_diag[kDiagCopies * 32];
 // parse, emission + copy-out, everything else
 // ... and the blocks each wave took: min, max, sum over waves, waves
 __device__ unsigned long long g_diag_bw[4] = {~0ull, 0, 0, 0};
+// ... and per launch and ticket shard: start, exit, own / stolen blocks (ShardDiag)
+__device__ unsigned long long g_diag_shard[kShardDiagSize];
+int g_diag_launches = 0;
 #define KDIAG_DECL                                   \
     uint64_t _kt = __builtin_amdgcn_s_memtime();     \
     uint64_t _kacc[4] = {0, 0, 0, 0};                \
@@ -1912,8 +1915,9 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
     lds8* D = L0 + kTableBytes;
     int64_t blk = blockIdx.x;
     if (blk >= nb) return;
-    const Tickets tks(a.tickets, 0);
-    uint32_t tk = tks.request(lane);  // the second block's, ahead of the first block's loads
+    Tickets tks(a.tickets, 0, nb, a.steal != 0);
+    Ticket tk = tks.request(lane);  // the second block's, ahead of the first block's loads
+    SHARD_DIAG_DECL;
     // block k -> (elements, source): one stream, or a batch of streams
     constexpr bool kBatch = (VAR & 256) != 0;
     auto blk_m = [&](int64_t k) {
@@ -2081,6 +2085,7 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
         // for the ticket would be a vmcnt(0) that drains them).  The block
         // after it is requested at once, ahead of the prefetch.
         const int64_t next = tks.block(tk, blk);
+        SHARD_DIAG_DREW(tks, next);
         if (next < nb) tk = tks.request(lane);
         if constexpr (kDefer) {
             // the previous block's record leaves now, behind this block's
@@ -2172,6 +2177,7 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
     }
     if constexpr (kDefer) flush_pending();
     KDIAG_FLUSH;
+    SHARD_DIAG_FLUSH(g_diag_shard, a.diag_slot, lane);
 }
 
 // Move each [BE32 c][c bytes] record from its scratch slot to out + offs[k].
@@ -2610,6 +2616,10 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
             EncArgs aa = a;
             aa.L = LL;
             aa.tickets = ticket_set(b, L, nb, set);
+            aa.steal = ticket_steal((int64_t)L.bs * L.E) ? 1 : 0;
+#ifdef BSHUF_DIAG
+            aa.diag_slot = g_diag_launches++;
+#endif
             // shift the base so blockIdx 0 is block `first`
             aa.in = a.in + first * (int64_t)L.bs * L.E;
             aa.scratch = a.scratch + first * b.slot;
@@ -2699,6 +2709,10 @@ hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
         auto go = [&](int64_t f0, int64_t f1, int set) -> hipError_t {
             EncArgs aa = a;
             aa.tickets = ticket_set(b, L, nb, set);
+            aa.steal = ticket_steal((int64_t)L.bs * L.E) ? 1 : 0;
+#ifdef BSHUF_DIAG
+            aa.diag_slot = g_diag_launches++;
+#endif
             aa.blk0 = f0;
             aa.scratch = a.scratch + f0 * b.slot;
             aa.foot = a.foot + f0;
@@ -2782,5 +2796,12 @@ extern "C" int bshuf_diag_read(unsigned long long* out) {
         return -1;
     static const unsigned long long z[bshuf::kDiagCopies * 32] = {0};
     return hipMemcpyToSymbol(HIP_SYMBOL(bshuf::g_diag), z, sizeof z) == hipSuccess ? 0 : -1;
+}
+// k_lz4_encode's per-shard table of the launches since the last read (ShardDiag,
+// bshuf_dev.h: kShardDiagSize words); returns their number, and resets.
+extern "C" int bshuf_diag_read_shards(unsigned long long* out) {
+    const int n = bshuf::g_diag_launches;
+    bshuf::g_diag_launches = 0;
+    return bshuf::shard_diag_read(HIP_SYMBOL(bshuf::g_diag_shard), out) == 0 ? n : -1;
 }
 #endif

@@ -59,7 +59,7 @@ bool prof_on() { return P().on; }
 // A/B knob: per calling thread, and only byte-identical variants are accepted
 // (the timing ablations that change the output exist in the diag build only).
 static thread_local int t_variant = 0;
-int tuning_variant() { return t_variant & ~(kNoPipe | kStaticSched | kTicketSched); }
+int tuning_variant() { return t_variant & ~(kNoPipe | kStaticSched | kTicketSched | kNoSteal); }
 // Dynamic block scheduling per kernel and block size (launch.h; the numbers:
 // DESIGN.md 6.5, profiles/dyn_sched).  4 GiB G1 per launch, static -> tickets:
 // k_lz4_encode 1.147 -> 1.093 ms, k_lz4_decode 3.10 -> 2.56 ms.  The encoder
@@ -71,6 +71,15 @@ bool ticket_sched(TicketKernel k, int64_t block_bytes) {
     if (t_variant & kStaticSched) return false;
     if (t_variant & kTicketSched) return true;
     return k == kTicketsEncode || block_bytes >= kDecodeTicketMinBlock;
+}
+// Stealing between the shards, k_lz4_encode (launch.h; profiles/ticket_steal):
+// 4 GiB G1 per launch 1.088 -> 1.047 ms, 1 KiB blocks 0.544 -> 0.527, 2 KiB
+// 0.398 -> 0.392; 128-byte blocks 0.728 -> 0.749, so not under 1 KiB.
+constexpr int64_t kStealMinBlock = 1024;
+bool ticket_steal(int64_t block_bytes) {
+    if (t_variant & kNoSteal) return false;
+    if (t_variant & kTicketSched) return true;  // "everywhere": also the tests' small blocks
+    return block_bytes >= kStealMinBlock;
 }
 
 namespace {
@@ -207,8 +216,9 @@ int bshuf_set_variant(int v) {
     // runs by lane_runs; any of
     // them | kNoPipe (1 << 20): no pipelined encode, | kStaticSched (1 << 24) /
     // kTicketSched (1 << 25): static / ticket block assignment in both
-    // persistent kernels (launch.h)
-    const int vv = v & ~(kNoPipe | kStaticSched | kTicketSched);
+    // persistent kernels, | kNoSteal (1 << 26): a wave leaves when its own
+    // ticket shard runs out (launch.h)
+    const int vv = v & ~(kNoPipe | kStaticSched | kTicketSched | kNoSteal);
     if (vv != 0 && vv != 2 && vv != 4 && vv != 8 && vv != 16 && vv != 32 && vv != 64 && vv != 128 && vv != 512 && vv != 1024 && vv != 2048 && vv != 4096 && vv != 8192 && vv != 16384 && vv != 24576 && vv != 40960 && vv != 57344 && vv != 65536 && vv != 319488 &&
         vv != 172032 && vv != 450560 &&
         vv != 2793472 && vv != 3072000)

@@ -1,8 +1,10 @@
-// Host build of the decoder's scan state machine (lz4_scan.h) for the CPU
-// test suite (tests/test_scan_host.py).  Not part of the product library.
+// Host build of the decoder's scan state machine (lz4_scan.h) and of the
+// ticket-stealing arithmetic (ticket_steal.h) for the CPU test suite.  Not part
+// of the product library.
 #include <stdint.h>
 
 #include "lz4_scan.h"
+#include "ticket_steal.h"
 
 namespace {
 struct HostReader {
@@ -26,4 +28,19 @@ extern "C" int bshuf_hostcheck_scan(const uint8_t* payload, int clen, int n, uin
     const int r = bshuf::scan_block(rd, clen, n, out, cnt);
     *nseq = cnt;
     return r;
+}
+
+// ticket_steal.h as the kernels use it
+extern "C" int bshuf_hostcheck_ticket_shards(void) { return bshuf::kTicketShards; }
+extern "C" int64_t bshuf_hostcheck_ticket_limit(int64_t first, int64_t G, int64_t end, int shard) {
+    return bshuf::ticket_limit(first, G, end, shard);
+}
+extern "C" uint32_t bshuf_hostcheck_ticket_remaining(int64_t limit, uint32_t drawn) {
+    return bshuf::ticket_remaining(limit, drawn);
+}
+// remaining: kTicketShards words
+extern "C" int bshuf_hostcheck_ticket_victim(const uint32_t* remaining, int own) {
+    uint32_t r[bshuf::kTicketShards];
+    for (int c = 0; c < bshuf::kTicketShards; c++) r[c] = remaining[c];
+    return bshuf::ticket_victim(r, own);
 }
