@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "bshuf_dev.h"
+#include "pipe_segments.h"
 
 namespace bshuf {
 
@@ -25,32 +26,57 @@ class ProfScope {
 };
 
 // Kernel-variant knob for A/B measurements (bshuf_set_variant, per thread,
-// byte-identical variants only); 0 = default.  The kNoPipe, kStaticSched,
-// kTicketSched and kNoSteal bits are not part of the variant (pipe_ctx /
-// ticket_sched / ticket_steal read them).
+// byte-identical variants only); 0 = default.  The kNoPipe, kNoOverlap,
+// kAltSegments, kWideCompact, kStaticSched, kTicketSched and kNoSteal bits are not part of
+// the variant (pipe_ctx / pipe_overlap / pipe_schedule / ticket_sched /
+// ticket_steal read them).
 int tuning_variant();
 #ifdef BSHUF_DIAG
 int diag_variant();  // timing ablations (wrong output), diag build only
 #endif
 
-// Pipelined encode.  A long encode runs as kPipeSegs launches of the parse
-// kernel on the caller's stream, and each segment's offset scan + compaction
-// on a per-thread side stream as soon as that segment is parsed, so the
-// HBM-bound compaction overlaps the next segment's (LDS- and latency-bound)
-// parse.  pipe_ctx(s) returns the calling thread's side stream on
-// the current device and its fork / join events, or nullptr: pipelining off
-// (bshuf_set_variant bit kNoPipe), `s` being captured into a graph, or no
-// side stream.  Every fork is joined back into `s` before the call returns,
-// so callers see one stream-ordered operation as before.
-constexpr int kPipeSegs = 8;
+// Pipelined encode.  A long encode runs as several launches of the parse
+// kernel (the segments of pipe_segments.h), and each segment's offset scan +
+// compaction on a per-thread side stream as soon as that segment is parsed, so
+// the HBM-bound compaction overlaps the next segment's (LDS- and latency-bound)
+// parse.  The parse launches alternate between the caller's stream (even
+// segments) and a second per-thread stream `par` (odd ones): launch i + 1 is
+// ordered only behind launch i - 1, so its workgroups wait in the dispatcher
+// and take each LDS slot the moment a wave of launch i exits, instead of the
+// whole launch waiting for the last wave of launch i and a launch gap.  At
+// most two parse launches are in flight.  Segments share nothing but the
+// read-only input: blocks, scratch slots, foot entries and ticket sets are
+// their own, and all ordering is by events (no kernel waits on memory another
+// running kernel writes).  With two launches in flight no CU drains between
+// segments, so everything on the side stream is single-wave workgroups of few
+// registers, which the dispatcher places beside six resident parse waves: the
+// segment-local scan k_seg_sums + k_seg_scan and the compaction
+// k_compact_t<1, 2> (lz4_encode.hip).  pipe_ctx(s) returns the calling thread's streams on
+// the current device and their fork / join events, or nullptr: pipelining off
+// (bshuf_set_variant bit kNoPipe), `s` being captured into a graph, or a
+// stream or event that could not be created.  Every fork is joined back into
+// `s` before the call returns, also after an error, so callers see one
+// stream-ordered operation as before.  With bit kNoOverlap, and while
+// per-kernel timing is on (prof_on(): an event pair around a launch queued
+// behind another would time the queueing too), every parse runs on `s`, one
+// after the other.
+constexpr int kPipeSegs = kPipeSegsMax;    // segments of the longest schedule
 constexpr int64_t kPipeMinBlocks = 65536;  // shorter calls run unsegmented
-constexpr int kPipeEvents = kPipeSegs + 2;  // fork, one per segment, join
+constexpr int kPipeEvents = kPipeSegs + 3;  // fork, one per segment, par's join, side's join
 constexpr int kNoPipe = 1 << 20;  // no pipelined encode
+constexpr int kNoOverlap = 1 << 27;  // pipelined encode with every parse on the caller's stream
+constexpr int kAltSegments = 1 << 28;  // the segment schedule that is not the default (A/B)
+constexpr int kWideCompact = 1 << 29;  // side-stream compaction by the 256-thread k_compact (A/B)
+constexpr int kPipeScheduleDefault = kPipeEqual;
 struct PipeCtx {
     hipStream_t side = nullptr;
+    hipStream_t par = nullptr;
     hipEvent_t ev[kPipeEvents] = {};
 };
 PipeCtx* pipe_ctx(hipStream_t s);
+bool pipe_overlap();   // parse launches on two streams (not kNoOverlap, not prof_on())
+int pipe_schedule();   // PipeSchedule of the calling thread
+bool pipe_slim_compact();  // side-stream compaction by k_compact_t<1, 2> (not kWideCompact)
 // s waits for everything enqueued on `from` so far (event ev)
 hipError_t stream_after(hipStream_t s, hipStream_t from, hipEvent_t ev);
 
@@ -84,6 +110,7 @@ constexpr int kEncTicketSets = kPipeSegs;  // unsegmented encodes use one or two
 constexpr int kStaticSched = 1 << 24;  // static block assignment in both kernels
 constexpr int kTicketSched = 1 << 25;  // tickets in both kernels at every block size
 constexpr int kNoSteal = 1 << 26;      // no stealing between ticket shards
+constexpr int kSideBits = kNoPipe | kNoOverlap | kAltSegments | kWideCompact | kStaticSched | kTicketSched | kNoSteal;
 enum TicketKernel { kTicketsEncode, kTicketsDecode };
 bool ticket_sched(TicketKernel k, int64_t block_bytes);
 bool ticket_steal(int64_t block_bytes);  // k_lz4_encode only
@@ -135,7 +162,7 @@ struct EncodeBufs {
     uint64_t* foot;     // nblocks + 1 u64: 4 + c per block, last = 0; behind it
                         // kEncTicketSets sets of ticket counters
     uint64_t* offs;     // nblocks + 1 u64: exclusive scan of foot
-    void* scan_tmp;     // hipcub temp storage
+    void* scan_tmp;     // hipcub temp storage; the pipelined path's tile sums
     size_t scan_tmp_bytes;
     uint8_t* shuf = nullptr;     // large blocks: the bit-transposed input
     uint32_t* tables = nullptr;  // large blocks: kLargeTableWords per block

@@ -2190,8 +2190,15 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
 // chunks per lane are loaded before any is stored.  One WAVE per record, four
 // records per 256-thread workgroup; records first .. nb-1 (a pipelined
 // segment, or all).
+// The pipelined encode's side stream runs the slim form instead
+// (k_compact_t<1, 2>): one wave per workgroup and two chunks per lane in
+// flight, 44 VGPRs.  Six resident parse waves leave a CU 48 VGPRs on two of its
+// SIMDs, so a 256-thread workgroup of 60 VGPRs finds no room there until a
+// parse launch drains, and with two parse launches in flight none does; single
+// waves of at most 48 VGPRs are placed on any SIMD beside the parse.
 constexpr int kCompactPerWg = 4;
 constexpr int kCompactUnroll = 4;
+constexpr int kCompactSideUnroll = 2;
 
 // 16 bytes at byte offset t (0..15, wave-uniform) of the 32-byte pair a|b.
 __device__ __forceinline__ u32x4 pair_bytes(const u32x4 a, const u32x4 b, int t) {
@@ -2215,13 +2222,12 @@ __device__ __forceinline__ u32x4 pair_bytes(const u32x4 a, const u32x4 b, int t)
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_compact(const uint8_t* __restrict__ scratch, int64_t slot,
-                                                 const uint64_t* __restrict__ offs,
-                                                 uint8_t* __restrict__ out, const Seg* segs,
-                                                 const uint32_t* __restrict__ blk_seg,
-                                                 uint64_t* __restrict__ block_offsets, int64_t first,
-                                                 int64_t nb) {
-    const int64_t blk = first + (int64_t)blockIdx.x * kCompactPerWg + (threadIdx.x >> 6);
+template <int PER_WG, int UNROLL>
+__global__ __launch_bounds__(kWave * PER_WG) void k_compact_t(
+    const uint8_t* __restrict__ scratch, int64_t slot, const uint64_t* __restrict__ offs,
+    uint8_t* __restrict__ out, const Seg* segs, const uint32_t* __restrict__ blk_seg,
+    uint64_t* __restrict__ block_offsets, int64_t first, int64_t nb) {
+    const int64_t blk = first + (int64_t)blockIdx.x * PER_WG + (threadIdx.x >> 6);
     const int tid = threadIdx.x & 63;
     if (blk >= nb) return;
     uint64_t rel0 = offs[blk];
@@ -2241,10 +2247,10 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t* __restrict__ scr
     const int m = (int)(dst0 & 15);
     const int gshift = m ? 1 : 0, t = m ? 16 - m : 0;
     gbl8* const d0 = (gbl8*)(dst0 & ~(uintptr_t)15);
-    for (int64_t jb = 0; jb < nq; jb += kWave * kCompactUnroll) {
-        u32x4 A[kCompactUnroll], Bv[kCompactUnroll];
+    for (int64_t jb = 0; jb < nq; jb += kWave * UNROLL) {
+        u32x4 A[UNROLL], Bv[UNROLL];
 #pragma unroll
-        for (int u = 0; u < kCompactUnroll; u++) {
+        for (int u = 0; u < UNROLL; u++) {
             const int64_t j = jb + u * kWave + tid;
             const int64_t g = j - gshift;
             A[u] = u32x4{0u, 0u, 0u, 0u};
@@ -2255,7 +2261,7 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t* __restrict__ scr
             }
         }
 #pragma unroll
-        for (int u = 0; u < kCompactUnroll; u++) {
+        for (int u = 0; u < UNROLL; u++) {
             const int64_t j = jb + u * kWave + tid;
             if (j >= nq) continue;
             const int64_t s = 16 * j - m;
@@ -2272,6 +2278,8 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t* __restrict__ scr
         }
     }
 }
+
+constexpr auto k_compact = k_compact_t<kCompactPerWg, kCompactUnroll>;
 
 // Blocks too large for the LDS (above max_lds_encode_bytes): one wave per
 // block runs the same wave-parallel parse (lz4_encode_block) with only the
@@ -2506,20 +2514,19 @@ int64_t max_device_block_bytes() { return 160 * 1024 - kTableBytes - 64; }
 
 namespace {
 
-// Pipelined encode (launch.h): parse segment i on s (enc(f_i, f_i+1)), then on
-// the side stream, as soon as it is parsed, the offset scan over blocks
-// [0, f_i+1) and the compaction of [f_i, f_i+1) -- overlapping the parse of
-// later segments (whose waves raise their issue priority, s_setprio, so the
-// compaction takes the issue slots the parse's dependency chain leaves idle).
-// The scan (hipcub) needs LDS, which a running parse holds on every CU, so it
-// starts as a parse segment drains, and the compaction behind it fills the
-// drain: measured on one box (profiles/r04/pipe), 4 GiB G1 compress 11.47 ->
-// 11.12 ms with 8 segments, 11.14 with 4; an LDS-free one-wave scan that let
-// the compaction run beside the parse body instead gained only 11.47 -> 11.25 /
-// 11.38 ms.  The scan of segment i reads foot[f_i+1], which segment i+1 may be
-// writing; that element feeds no output of the scan.  foot[nb] = 0 and the
-// ticket counters behind it (set i for segment i) are zeroed by the caller's
-// fill before the fork.  The side stream joins s before `finish` runs on s.
+// Pipelined encode (launch.h): parse segment i (enc(f_i, f_i+1), the bounds of
+// pipe_segments.h) on s or, every other one, on the par stream; then on the
+// side stream, as soon as it is parsed, the offset scan and the compaction of
+// [f_i, f_i+1) -- beside the parse of later segments (whose waves raise their
+// issue priority, s_setprio, so the compaction takes the issue slots the
+// parse's dependency chain leaves idle).  With two parse launches in flight a
+// CU's LDS never drains between segments, so the scan is the segment-local
+// k_seg_scan, which fits beside a resident parse; the device-wide hipcub scan
+// over [0, f_i+1] it replaced needed the drains to get its LDS (measured then,
+// profiles/r04/pipe: 4 GiB G1 compress 11.47 -> 11.12 ms with 8 segments, 11.14
+// with 4).  foot[nb] = 0 and the ticket counters behind it (set i for segment
+// i) are zeroed by the caller's fill before the forks.  par and the side stream
+// join s before `finish` runs on s.
 // foot[nb] = 0 (the offset scan's last input) and, in the same fill, the
 // call's ticket counters behind it: zero before the first parse launch,
 // whatever the caller's workspace held.
@@ -2533,34 +2540,154 @@ uint32_t* ticket_set(const EncodeBufs& b, const Layout& L, int64_t nb, int set) 
     return reinterpret_cast<uint32_t*>(b.foot + nb + 1) + (size_t)set * (kTicketSetBytes / sizeof(uint32_t));
 }
 
+// Segment-local offset scan of the pipelined encode: offs[f0 .. f1] from
+// foot[f0, f1) and the seed offs[f0] (0 for the call's first segment), in two
+// small launches over at most kSegScanTiles tiles: the tiles' sums, then every
+// tile adds up the sums in front of it and scans its own elements.  One wave
+// per tile, 256 elements at a time (four per lane, shuffles across the lanes),
+// no LDS and few registers: beside six resident parse waves a CU has three LDS
+// granules left and, on the two SIMDs that hold two of them, 48 VGPRs (E = 2)
+// or none (E = 4, 8), so only single waves are sure of a place -- on the SIMDs
+// that hold one parse wave.  A 256-thread workgroup needs all four SIMDs at
+// once and waited for the next parse launch to drain (E = 4: 8 ms per scan).
+// It reads nothing a later segment's parse writes.
+constexpr int kSegScanPerLane = 4;
+constexpr int kSegScanStep = kWave * kSegScanPerLane;  // elements per wave and iteration
+constexpr int kSegScanTiles = 1024;       // tile sums: 8 KiB of the scan's temp storage
+constexpr int64_t kSegScanMinTile = 1024;  // elements; a multiple of kSegScanStep
+
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int lane) {
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane, kWave);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane, kWave);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, kWave);
+    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, kWave);
+    return ((uint64_t)hi << 32) | lo;
+}
+// Sum of v over the wave, in every lane.
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, kWave);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, kWave);
+        v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kWave) void k_seg_sums(const uint64_t* __restrict__ foot,
+                                                    uint64_t* __restrict__ sums, int64_t f0, int64_t f1,
+                                                    int64_t tile) {
+    const int64_t t0 = f0 + (int64_t)blockIdx.x * tile;
+    const int64_t t1 = t0 + tile < f1 ? t0 + tile : f1;
+    uint64_t v = 0;
+    for (int64_t i = t0 + threadIdx.x; i < t1; i += kWave) v += foot[i];
+    v = wave_sum(v);
+    if (threadIdx.x == 0) sums[blockIdx.x] = v;
+}
+
+__global__ __launch_bounds__(kWave) void k_seg_scan(const uint64_t* __restrict__ foot,
+                                                    const uint64_t* __restrict__ sums, uint64_t* offs,
+                                                    int64_t f0, int64_t f1, int64_t tile, int seeded) {
+    const int lane = threadIdx.x;
+    const int64_t t0 = f0 + (int64_t)blockIdx.x * tile;
+    const int64_t t1 = t0 + tile < f1 ? t0 + tile : f1;
+    // the offset of the tile's first element: the seed + the tiles in front
+    uint64_t v = 0;
+    for (int u = lane; u < (int)blockIdx.x; u += kWave) v += sums[u];
+    uint64_t base = wave_sum(v) + (seeded ? offs[f0] : 0);
+    for (int64_t c = t0; c < t1; c += kSegScanStep) {
+        const int64_t i0 = c + (int64_t)lane * kSegScanPerLane;
+        uint64_t x[kSegScanPerLane], tot = 0;
+#pragma unroll
+        for (int k = 0; k < kSegScanPerLane; k++) {
+            x[k] = i0 + k < t1 ? foot[i0 + k] : 0;
+            tot += x[k];
+        }
+        uint64_t inc = tot;  // inclusive scan of the lanes' totals
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const uint64_t y = shfl_up_u64(inc, d);
+            if (lane >= d) inc += y;
+        }
+        uint64_t o = base + inc - tot;
+#pragma unroll
+        for (int k = 0; k < kSegScanPerLane; k++) {
+            // offs[f0] of a seeded segment is the previous segment's, read above by every tile
+            if (i0 + k < t1 && !(seeded && i0 + k == f0)) offs[i0 + k] = o;
+            o += x[k];
+        }
+        base += shfl_u64(inc, kWave - 1);
+    }
+    if (t1 == f1 && lane == 0) offs[f1] = base;  // the last tile: the segment's end
+}
+
+// Tile length for a segment of n blocks: at most kSegScanTiles tiles.
+int64_t seg_scan_tile(int64_t n) {
+    const int64_t t = (n + kSegScanTiles - 1) / kSegScanTiles;
+    return std::max(kSegScanMinTile, (t + kSegScanStep - 1) / kSegScanStep * kSegScanStep);
+}
+
+hipError_t launch_seg_scan(const EncodeBufs& b, int64_t f0, int64_t f1, bool seeded, hipStream_t s) {
+    if (f1 <= f0) return hipSuccess;
+    if (b.scan_tmp_bytes < kSegScanTiles * sizeof(uint64_t)) return hipErrorInvalidValue;
+    const int64_t tile = seg_scan_tile(f1 - f0);
+    const unsigned tiles = (unsigned)((f1 - f0 + tile - 1) / tile);
+    uint64_t* sums = static_cast<uint64_t*>(b.scan_tmp);
+    // "_side": beside the parse (bench.py keeps these apart from the step's
+    // serial kernels)
+    ProfScope prof("scan_block_offsets_side", s);
+    if (tiles > 1) {
+        hipLaunchKernelGGL(k_seg_sums, dim3(tiles), dim3(kWave), 0, s, b.foot, sums, f0, f1, tile);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_seg_scan, dim3(tiles), dim3(kWave), 0, s, b.foot, sums, b.offs, f0, f1, tile,
+                       seeded ? 1 : 0);
+    return hipGetLastError();
+}
+
 template <class Enc, class Fin>
 hipError_t encode_pipelined(int64_t nb, hipStream_t s, PipeCtx* pc, const EncodeBufs& b, Enc enc,
                             uint8_t* out, const Seg* segs, const uint32_t* blk_seg,
                             uint64_t* block_offsets, Fin finish) {
+    const bool overlap = pipe_overlap();
+    const int sched = pipe_schedule(), nseg = pipe_seg_count(sched);
+    const bool slim = pipe_slim_compact();
+    // the caller's fill (foot[nb], the ticket sets) is in front of both forks
     hipError_t e = stream_after(pc->side, s, pc->ev[0]);
-    for (int i = 0; i < kPipeSegs && e == hipSuccess; i++) {
-        const int64_t f0 = nb * i / kPipeSegs, f1 = nb * (i + 1) / kPipeSegs;
+    if (e == hipSuccess && overlap) e = hipStreamWaitEvent(pc->par, pc->ev[0], 0);
+    bool forked = e == hipSuccess && overlap, seeded = false;
+    for (int i = 0, k = 0; i < nseg && e == hipSuccess; i++) {
+        const int64_t f0 = pipe_seg_bound(nb, sched, i), f1 = pipe_seg_bound(nb, sched, i + 1);
         if (f1 == f0) continue;
-        e = enc(f0, f1, i);
-        if (e == hipSuccess) e = stream_after(pc->side, s, pc->ev[1 + i]);
+        // parse launches alternate between s and par: launch k + 1 is ordered
+        // behind launch k - 1 only
+        hipStream_t ps = overlap && (k++ & 1) ? pc->par : s;
+        e = enc(f0, f1, i, ps);
+        if (e == hipSuccess) e = stream_after(pc->side, ps, pc->ev[1 + i]);
         if (e != hipSuccess) break;
-        {
-            size_t tmp = b.scan_tmp_bytes;
-            // "_side": beside the parse (bench.py keeps these apart from the
-            // step's serial kernels)
-            ProfScope prof("scan_block_offsets_side", pc->side);
-            e = hipcub::DeviceScan::ExclusiveSum(b.scan_tmp, tmp, b.foot, b.offs, (int)(f1 + 1), pc->side);
-        }
+        e = launch_seg_scan(b, f0, f1, seeded, pc->side);
+        seeded = true;
         if (e != hipSuccess) break;
         ProfScope prof("k_compact_side", pc->side);
-        hipLaunchKernelGGL(k_compact, dim3((unsigned)((f1 - f0 + kCompactPerWg - 1) / kCompactPerWg)),
-                           dim3(256), 0, pc->side, b.scratch, b.slot, b.offs, out, segs, blk_seg,
-                           block_offsets, f0, f1);
+        if (slim)
+            hipLaunchKernelGGL((k_compact_t<1, kCompactSideUnroll>), dim3((unsigned)(f1 - f0)), dim3(kWave), 0,
+                               pc->side, b.scratch, b.slot, b.offs, out, segs, blk_seg, block_offsets, f0,
+                               f1);
+        else
+            hipLaunchKernelGGL(k_compact, dim3((unsigned)((f1 - f0 + kCompactPerWg - 1) / kCompactPerWg)),
+                               dim3(256), 0, pc->side, b.scratch, b.slot, b.offs, out, segs, blk_seg,
+                               block_offsets, f0, f1);
         e = hipGetLastError();
     }
-    // join even after an error, so nothing of this call is left on the side stream unordered
+    // join even after an error, so nothing of this call is left on par or the side stream unordered
+    const hipError_t jp = forked ? stream_after(s, pc->par, pc->ev[kPipeEvents - 2]) : hipSuccess;
     const hipError_t j = stream_after(s, pc->side, pc->ev[kPipeEvents - 1]);
     if (e != hipSuccess) return e;
+    if (jp != hipSuccess) return jp;
     if (j != hipSuccess) return j;
     return finish(s);
 }
@@ -2584,7 +2711,8 @@ size_t encode_scan_tmp_bytes(int64_t nblocks) {
     size_t bytes = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                      (int)(nblocks + 1));
-    return bytes;
+    // the pipelined path keeps its scan's tile sums there (launch_seg_scan)
+    return std::max(bytes, kSegScanTiles * sizeof(uint64_t));
 }
 
 hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64_t tail_bytes,
@@ -2612,7 +2740,7 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
         const bool wide_last = L.last && (int64_t)L.last * L.E >= kU16TableLimit;
         const bool aligned = ((uintptr_t)in & 15) == 0;
         const int ek = aligned && (L.E == 1 || L.E == 2 || L.E == 4 || L.E == 8) ? L.E : 0;
-        auto go = [&](Layout LL, bool w, int64_t count, int64_t first, int set) -> hipError_t {
+        auto go = [&](Layout LL, bool w, int64_t count, int64_t first, int set, hipStream_t s) -> hipError_t {
             EncArgs aa = a;
             aa.L = LL;
             aa.tickets = ticket_set(b, L, nb, set);
@@ -2641,8 +2769,8 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
             return hipErrorInvalidValue;
         };
         PipeCtx* pc = (wide == wide_last || !L.last) && nb >= kPipeMinBlocks ? pipe_ctx(s) : nullptr;
-        if (pc) return encode_pipelined(nb, s, pc, b, [&](int64_t f0, int64_t f1, int set) {
-            return go(L, wide, f1 - f0, f0, set);
+        if (pc) return encode_pipelined(nb, s, pc, b, [&](int64_t f0, int64_t f1, int set, hipStream_t ps) {
+            return go(L, wide, f1 - f0, f0, set, ps);
         }, out, nullptr, nullptr, nullptr, [&](hipStream_t st) {
             const uint8_t* tail_src = in + (L.nfull * (int64_t)L.bs + L.last) * L.E;
             ProfScope prof("k_encode_finish", st);
@@ -2651,12 +2779,12 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
             return hipGetLastError();
         });
         if (wide == wide_last || !L.last) {
-            e = go(L, wide, nb, 0, 0);
+            e = go(L, wide, nb, 0, 0, s);
         } else {
             Layout Lf = L;
             Lf.last = 0;
-            e = go(Lf, wide, L.nfull, 0, 0);
-            if (e == hipSuccess) e = go(L, wide_last, 1, L.nfull, 1);
+            e = go(Lf, wide, L.nfull, 0, 0, s);
+            if (e == hipSuccess) e = go(L, wide_last, 1, L.nfull, 1, s);
         }
         if (e != hipSuccess) return e;
     }
@@ -2706,7 +2834,7 @@ hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
         const int ek = aligned && (L.E == 1 || L.E == 2 || L.E == 4 || L.E == 8) ? L.E : 0;
         // blocks [f0, f1) of the batch: the segment table is indexed globally
         // (blk0), scratch slots and sizes relative to f0
-        auto go = [&](int64_t f0, int64_t f1, int set) -> hipError_t {
+        auto go = [&](int64_t f0, int64_t f1, int set, hipStream_t s) -> hipError_t {
             EncArgs aa = a;
             aa.tickets = ticket_set(b, L, nb, set);
             aa.steal = ticket_steal((int64_t)L.bs * L.E) ? 1 : 0;
@@ -2740,7 +2868,7 @@ hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
                                L.bs, L.E);
             return hipGetLastError();
         });
-        e = go(0, nb, 0);
+        e = go(0, nb, 0, s);
         if (e != hipSuccess) return e;
     }
     size_t tmp = b.scan_tmp_bytes;
@@ -2779,6 +2907,19 @@ hipError_t launch_seg_map(const Seg* segs, int nsegs, uint32_t* map, bool chunks
 }
 
 }  // namespace bshuf
+
+// Test hook: the pipelined encode's segment-local offset scan on device
+// arrays.  offs[f0 .. f1] from foot[f0, f1), seeded with offs[f0] (seeded != 0)
+// or 0; tmp: at least 8 KiB of device memory.  Returns 0 or -(HIP error).
+extern "C" int bshuf_seg_scan_dev(const uint64_t* foot, uint64_t* offs, void* tmp, size_t tmp_bytes,
+                                  int64_t f0, int64_t f1, int seeded, void* stream) {
+    bshuf::EncodeBufs b{};
+    b.foot = const_cast<uint64_t*>(foot);
+    b.offs = offs;
+    b.scan_tmp = tmp;
+    b.scan_tmp_bytes = tmp_bytes;
+    return -(int)bshuf::launch_seg_scan(b, f0, f1, seeded != 0, (hipStream_t)stream);
+}
 
 #ifdef BSHUF_DIAG
 // Diagnostic build only: read (and reset) the encoder's phase counters.

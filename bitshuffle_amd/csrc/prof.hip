@@ -59,7 +59,7 @@ bool prof_on() { return P().on; }
 // A/B knob: per calling thread, and only byte-identical variants are accepted
 // (the timing ablations that change the output exist in the diag build only).
 static thread_local int t_variant = 0;
-int tuning_variant() { return t_variant & ~(kNoPipe | kStaticSched | kTicketSched | kNoSteal); }
+int tuning_variant() { return t_variant & ~kSideBits; }
 // Dynamic block scheduling per kernel and block size (launch.h; the numbers:
 // DESIGN.md 6.5, profiles/dyn_sched).  4 GiB G1 per launch, static -> tickets:
 // k_lz4_encode 1.147 -> 1.093 ms, k_lz4_decode 3.10 -> 2.56 ms.  The encoder
@@ -93,9 +93,11 @@ struct PipeSet {
         for (PipeCtx& x : c) {
             if (!x.side) continue;
             (void)hipStreamSynchronize(x.side);
+            (void)hipStreamSynchronize(x.par);
             for (hipEvent_t& e : x.ev)
                 if (e) (void)hipEventDestroy(e);
             (void)hipStreamDestroy(x.side);
+            (void)hipStreamDestroy(x.par);
         }
     }
 };
@@ -110,7 +112,8 @@ PipeCtx* pipe_ctx(hipStream_t s) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kPipeDevices || t_pipe.bad[dev]) return nullptr;
     PipeCtx& x = t_pipe.c[dev];
     if (x.side) return &x;
-    bool ok = hipStreamCreateWithFlags(&x.side, hipStreamNonBlocking) == hipSuccess;
+    bool ok = hipStreamCreateWithFlags(&x.side, hipStreamNonBlocking) == hipSuccess &&
+              hipStreamCreateWithFlags(&x.par, hipStreamNonBlocking) == hipSuccess;
     for (int i = 0; ok && i < kPipeEvents; i++)
         ok = hipEventCreateWithFlags(&x.ev[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
@@ -119,6 +122,15 @@ PipeCtx* pipe_ctx(hipStream_t s) {
         return nullptr;
     }
     return &x;
+}
+
+// The two-stream parse schedule is a plain-run matter: per-kernel timing puts
+// an event pair around every launch, and a launch queued behind the one on the
+// other stream would be timed with its wait.
+bool pipe_overlap() { return !(t_variant & kNoOverlap) && !prof_on(); }
+bool pipe_slim_compact() { return !(t_variant & kWideCompact); }
+int pipe_schedule() {
+    return t_variant & kAltSegments ? (kPipeScheduleDefault + 1) % kPipeSchedules : kPipeScheduleDefault;
 }
 
 hipError_t stream_after(hipStream_t s, hipStream_t from, hipEvent_t ev) {
@@ -217,8 +229,11 @@ int bshuf_set_variant(int v) {
     // them | kNoPipe (1 << 20): no pipelined encode, | kStaticSched (1 << 24) /
     // kTicketSched (1 << 25): static / ticket block assignment in both
     // persistent kernels, | kNoSteal (1 << 26): a wave leaves when its own
-    // ticket shard runs out (launch.h)
-    const int vv = v & ~(kNoPipe | kStaticSched | kTicketSched | kNoSteal);
+    // ticket shard runs out, | kNoOverlap (1 << 27): the pipelined encode's
+    // parse launches all on the caller's stream, | kAltSegments (1 << 28): the
+    // pipelined encode's other segment schedule, | kWideCompact (1 << 29): its
+    // side-stream compaction by the 256-thread k_compact (launch.h)
+    const int vv = v & ~kSideBits;
     if (vv != 0 && vv != 2 && vv != 4 && vv != 8 && vv != 16 && vv != 32 && vv != 64 && vv != 128 && vv != 512 && vv != 1024 && vv != 2048 && vv != 4096 && vv != 8192 && vv != 16384 && vv != 24576 && vv != 40960 && vv != 57344 && vv != 65536 && vv != 319488 &&
         vv != 172032 && vv != 450560 &&
         vv != 2793472 && vv != 3072000)

@@ -1,9 +1,11 @@
-// Host build of the decoder's scan state machine (lz4_scan.h) and of the
-// ticket-stealing arithmetic (ticket_steal.h) for the CPU test suite.  Not part
-// of the product library.
+// Host build of the decoder's scan state machine (lz4_scan.h), of the
+// ticket-stealing arithmetic (ticket_steal.h) and of the pipelined encode's
+// segment bounds (pipe_segments.h) for the CPU test suite.  Not part of the
+// product library.
 #include <stdint.h>
 
 #include "lz4_scan.h"
+#include "pipe_segments.h"
 #include "ticket_steal.h"
 
 namespace {
@@ -28,6 +30,14 @@ extern "C" int bshuf_hostcheck_scan(const uint8_t* payload, int clen, int n, uin
     const int r = bshuf::scan_block(rd, clen, n, out, cnt);
     *nseq = cnt;
     return r;
+}
+
+// pipe_segments.h as the launcher uses it
+extern "C" int bshuf_hostcheck_pipe_schedules(void) { return bshuf::kPipeSchedules; }
+extern "C" int bshuf_hostcheck_pipe_segs_max(void) { return bshuf::kPipeSegsMax; }
+extern "C" int bshuf_hostcheck_pipe_seg_count(int schedule) { return bshuf::pipe_seg_count(schedule); }
+extern "C" int64_t bshuf_hostcheck_pipe_seg_bound(int64_t nb, int schedule, int i) {
+    return bshuf::pipe_seg_bound(nb, schedule, i);
 }
 
 // ticket_steal.h as the kernels use it
