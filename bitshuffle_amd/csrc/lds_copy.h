@@ -108,4 +108,43 @@ __device__ __forceinline__ void lane_len_run(lds8* S, int p, int cnt, uint32_t l
         if (i < cnt) S[p + i] = (uint8_t)(i + 1 < cnt ? 255u : last);
 }
 
+// The same in closed form, with no loop over a run's bytes.  The first J <= 4
+// bytes of a run as a value (byte i in bits 8i..8i+7; zero above the run's end),
+// for the run's own lane to merge into a masked dword write with the bytes next
+// to them (len_run_head), and the runs longer than J -- match lengths from 780,
+// a few lanes per block at most -- one after another by the whole wave, byte
+// J + i by lane i (lane_len_rest).  Writes only: nothing waits.
+template <int J>
+__device__ __forceinline__ uint32_t len_run_head(int cnt, uint32_t last) {
+    static_assert(J >= 1 && J <= 4, "at most one dword");
+    constexpr uint32_t all = 0xFFFFFFFFu >> (32 - 8 * J);
+    if (cnt > J) return all;
+    if (cnt <= 0) return 0u;
+    const uint32_t sh = 8u * (uint32_t)(cnt - 1);
+    return ((1u << sh) - 1u) | (last << sh);
+}
+template <int J>
+__device__ __forceinline__ void lane_len_rest(lds8* S, int p, int cnt, uint32_t last, int lane) {
+    for (uint64_t lm = __builtin_amdgcn_ballot_w64(cnt > J); lm; lm &= lm - 1) {
+        const int l = __builtin_ctzll(lm);
+        const int pl = __builtin_amdgcn_readlane(p, l), cl = __builtin_amdgcn_readlane(cnt, l);
+        const uint32_t ll = (uint32_t)__builtin_amdgcn_readlane((int)last, l);
+        for (int i0 = J; i0 < cl; i0 += kWave) {
+            const int i = i0 + lane;
+            if (i < cl) S[pl + i] = (uint8_t)(i + 1 < cl ? 255u : ll);
+        }
+    }
+}
+
+// Up to 5 bytes (value v, byte i in bits 8i..; nbytes of them, 0 allowed) at
+// byte address p as two masked dword writes: the bytes span at most two dwords.
+__device__ __forceinline__ void lane_put5(lds8* S, int p, uint64_t v, int nbytes) {
+    const uint32_t sh = 8u * (uint32_t)(p & 3);
+    const uint64_t m = ((1ull << (8 * nbytes)) - 1ull) << sh;
+    const uint64_t d = (v << sh) & m;
+    const uint32_t a = (uint32_t)(uintptr_t)(S + (p & ~3));
+    lds_write_masked(a, (uint32_t)m, (uint32_t)d);
+    lds_write_masked(a + 4u, (uint32_t)(m >> 32), (uint32_t)(d >> 32));
+}
+
 }  // namespace bshuf

@@ -1113,7 +1113,8 @@ struct SeqOutLane0 {
     }
 };
 
-// BSHUF_SCAN_BIG_LDS=0 (default): the window lives in registers instead --
+// BSHUF_SCAN_BIG_LDS=0 (A/B builds only; the shipped default is 1, the LDS
+// window of WaveReader): the window lives in registers instead --
 // 1 KiB of the record in four VGPRs (lane l, dword d: bytes 4l + 256d) plus the
 // next 1 KiB already in flight -- and a byte is one v_readlane of a uniform
 // lane, so the whole walk runs on the scalar unit without an LDS round trip per

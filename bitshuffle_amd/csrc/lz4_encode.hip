@@ -78,10 +78,35 @@ __device__ unsigned long long g_diag_bw[4] = {~0ull, 0, 0, 0};
 // ... and per launch and ticket shard: start, exit, own / stolen blocks (ShardDiag)
 __device__ unsigned long long g_diag_shard[kShardDiagSize];
 int g_diag_launches = 0;
+// ... and the emission's sub-phases (slots 24..27: descriptor read + prefix
+// sum, token / length / offset bytes, per-lane literal runs, the wave's literal
+// runs) and events (28..31: runs copied per lane, runs copied by the wave, wave
+// copy steps, length-run steps).  A stamp waits for every LDS operation issued
+// before it (s_memtime's result shares their counter), so the sub-phases do
+// not overlap as they do in the product build.
+__device__ __forceinline__ int wave_max(int v) {
+    for (int d = 32; d; d >>= 1) v = max(v, __shfl_xor(v, d));
+    return v;
+}
+struct EmitDiag {
+    uint64_t t = 0;
+    uint64_t acc[4] = {0, 0, 0, 0};
+    uint32_t cnt[4] = {0, 0, 0, 0};
+};
+#define ESTART (ed.t = __builtin_amdgcn_s_memtime())
+#define ESTAMP(i)                                         \
+    do {                                                  \
+        const uint64_t _n = __builtin_amdgcn_s_memtime(); \
+        ed.acc[i] += _n - ed.t;                           \
+        ed.t = _n;                                        \
+    } while (0)
+#define ECOUNT(i, v) (ed.cnt[i] += (uint32_t)(v))
 #define KDIAG_DECL                                   \
     uint64_t _kt = __builtin_amdgcn_s_memtime();     \
     uint64_t _kacc[4] = {0, 0, 0, 0};                \
+    EmitDiag _ed;                                    \
     unsigned long long _kblocks = 0;
+#define KEMITDIAG _ed
 #define KBLOCK (++_kblocks)
 #define KSTAMP(i)                                       \
     do {                                                \
@@ -94,6 +119,12 @@ int g_diag_launches = 0;
         if (lane == 0)                                                                  \
             for (int _i = 0; _i < 4; _i++)                                              \
                 atomicAdd(&g_diag[(blockIdx.x % kDiagCopies) * 32 + 16 + _i], _kacc[_i]); \
+        if (lane == 0)                                                                  \
+            for (int _i = 0; _i < 4; _i++) {                                            \
+                atomicAdd(&g_diag[(blockIdx.x % kDiagCopies) * 32 + 24 + _i], _ed.acc[_i]); \
+                atomicAdd(&g_diag[(blockIdx.x % kDiagCopies) * 32 + 28 + _i],           \
+                          (unsigned long long)_ed.cnt[_i]);                             \
+            }                                                                           \
         if (lane == 0) {                                                                \
             atomicMin(&g_diag_bw[0], _kblocks);                                         \
             atomicMax(&g_diag_bw[1], _kblocks);                                         \
@@ -102,7 +133,12 @@ int g_diag_launches = 0;
         }                                                                               \
     } while (0)
 #else
-#define KDIAG_DECL
+struct EmitDiag {};
+#define ESTART ((void)0)
+#define ESTAMP(i) ((void)0)
+#define ECOUNT(i, v) ((void)0)
+#define KDIAG_DECL EmitDiag _ed;
+#define KEMITDIAG _ed
 #define KBLOCK ((void)0)
 #define KSTAMP(i) ((void)0)
 #define KDIAG_FLUSH ((void)0)
@@ -242,7 +278,9 @@ constexpr int kWinBytes = 4 * kWave;  // bytes one dword-per-lane wave access co
 //    descriptor slots, and the A/B variant 2).
 // ---------------------------------------------------------------------------
 
-constexpr int kLaneRun = 128;              // emission: longest literal run copied per lane
+constexpr int kLaneRun = 128;              // emission: longest literal run copied per lane (emit_sequences)
+constexpr int kFlatLaneRun = 32;           // ... by emit_sequences_flat
+constexpr int kVarEmitFlat = 4194304;      // VAR bit: emit_sequences_flat (the default)
 constexpr int kLaneRunMin = 4;             // ... when the batch has at least this many long runs
 constexpr int kDescMax = 256;              // descriptor slots per block
 constexpr int kDescBytes = 8 * kDescMax;   // LDS behind the block
@@ -334,36 +372,12 @@ struct EmitBytes {
     }
 };
 
-// Each lane with `mine` copies its literal run of n bytes (1..kLaneRun) from
-// D[sp] to S[dp] (LDS, disjoint; the block D has readable bytes past its end):
-// destination dword t is v_alignbyte of source dwords t and t+1 at one shift
-// for the whole run, so only the head and tail dwords (shared with the
-// token / length / offset bytes around the run) take masked writes -- the
-// whole dwords between go out as plain writes, four per step, with no
-// per-piece mask arithmetic (lane_copy16 recomputes five masks per 16 bytes).
 #ifndef BSHUF_RUNS_PIPE
 #define BSHUF_RUNS_PIPE 1
 #endif
-__device__ __forceinline__ void lane_runs(const lds8* D, int sp, lds8* S, int dp, int n, bool mine) {
-    const int k = dp & 3;
-    const int b = sp - k;  // source byte of destination dword 0's byte 0 (may be < 0: masked off)
-    const uint32_t r = (uint32_t)(b & 3);
-    const lds32* W = (const lds32*)(D + (b & ~3));
-    lds32* O = (lds32*)(S + (dp & ~3));
-    const int nd = ((dp + n + 3) >> 2) - (dp >> 2);  // destination dwords touched
-    if (mine) {
-        const int e = dp + n - 4 * ((dp + n - 1) >> 2);  // bytes of the run in its last dword, 1..4
-        const uint32_t mt = e >= 4 ? ~0u : ((1u << (8 * e)) - 1u);
-        uint32_t mh = ~0u << (8 * k);
-        if (nd == 1) mh &= mt;
-        const uint32_t vh = __builtin_amdgcn_alignbyte(W[1], W[0], r);
-        lds_write_masked(lds_addr((lds8*)O), mh, vh & mh);
-        if (nd > 1) {
-            const uint32_t vt = __builtin_amdgcn_alignbyte(W[nd], W[nd - 1], r);
-            lds_write_masked(lds_addr((lds8*)(O + nd - 1)), mt, vt & mt);
-        }
-    }
-    const int last = mine ? nd - 2 : 0;  // interior dwords 1 .. last
+// Every lane copies the interior destination dwords 1 .. last of its run
+// (last <= 0: none): O[t] = v_alignbyte(W[t + 1], W[t], r), four per step.
+__device__ __forceinline__ void lane_runs_interior(const lds32* W, lds32* O, const uint32_t r, const int last) {
 #if BSHUF_RUNS_PIPE
     // software-pipelined: the next step's four source dwords are read before
     // this step's four writes (block and record are disjoint LDS), so a step
@@ -411,6 +425,34 @@ __device__ __forceinline__ void lane_runs(const lds8* D, int sp, lds8* S, int dp
     }
 #endif
 }
+// Each lane with `mine` copies its literal run of n bytes (1..kLaneRun) from
+// D[sp] to S[dp] (LDS, disjoint; the block D has readable bytes past its end):
+// destination dword t is v_alignbyte of source dwords t and t+1 at one shift
+// for the whole run, so only the head and tail dwords (shared with the
+// token / length / offset bytes around the run) take masked writes -- the
+// whole dwords between go out as plain writes, four per step, with no
+// per-piece mask arithmetic (lane_copy16 recomputes five masks per 16 bytes).
+__device__ __forceinline__ void lane_runs(const lds8* D, int sp, lds8* S, int dp, int n, bool mine) {
+    const int k = dp & 3;
+    const int b = sp - k;  // source byte of destination dword 0's byte 0 (may be < 0: masked off)
+    const uint32_t r = (uint32_t)(b & 3);
+    const lds32* W = (const lds32*)(D + (b & ~3));
+    lds32* O = (lds32*)(S + (dp & ~3));
+    const int nd = ((dp + n + 3) >> 2) - (dp >> 2);  // destination dwords touched
+    if (mine) {
+        const int e = dp + n - 4 * ((dp + n - 1) >> 2);  // bytes of the run in its last dword, 1..4
+        const uint32_t mt = e >= 4 ? ~0u : ((1u << (8 * e)) - 1u);
+        uint32_t mh = ~0u << (8 * k);
+        if (nd == 1) mh &= mt;
+        const uint32_t vh = __builtin_amdgcn_alignbyte(W[1], W[0], r);
+        lds_write_masked(lds_addr((lds8*)O), mh, vh & mh);
+        if (nd > 1) {
+            const uint32_t vt = __builtin_amdgcn_alignbyte(W[nd], W[nd - 1], r);
+            lds_write_masked(lds_addr((lds8*)(O + nd - 1)), mt, vt & mt);
+        }
+    }
+    lane_runs_interior(W, O, r, mine ? nd - 2 : 0);
+}
 
 // Builds the LZ4 bytes of a parsed block from its descriptors, wave-parallel
 // (lane = sequence; a prefix sum places every sequence): record payload at
@@ -419,9 +461,11 @@ __device__ __forceinline__ void lane_runs(const lds8* D, int sp, lds8* S, int dp
 // 2097152), else lane_copy16 pieces.
 template <bool kRuns, class Em>
 __device__ __forceinline__ int emit_sequences(const lds8* D, const Em& em, const int n, lds8* S,
-                                              const int lane) {
+                                              const int lane, EmitDiag& ed) {
+    (void)ed;
     const int ns = em.ns, la = em.la;
     int opb = 4;
+    ESTART;
     for (int b0 = 0; b0 <= ns; b0 += kWave) {
         const int s = b0 + lane;
         const bool m = s < ns;
@@ -440,8 +484,11 @@ __device__ __forceinline__ int emit_sequences(const lds8* D, const Em& em, const
         const int incl = wave_incl_sum(len, lane);
         const int op = opb + incl - len;
         opb += __builtin_amdgcn_readlane(incl, kWave - 1);
+        ESTAMP(0);
         if (act) S[op] = (uint8_t)((min(lit, 15) << 4) | (m ? min(mc, 15) : 0));
         lane_len_run(S, op + 1, le, (uint32_t)(lit - 15) % 255u);
+        ECOUNT(3, wave_max(le) + wave_max(me));
+        ESTAMP(1);
         const int lp = op + 1 + le, lsrc = ip - lit;
         // With several long runs in the batch (literal-heavy data): runs of up
         // to kLaneRun bytes are copied by their own lanes in 16-byte pieces,
@@ -449,6 +496,7 @@ __device__ __forceinline__ int emit_sequences(const lds8* D, const Em& em, const
         // masked writes); otherwise, and for longer runs, run by run by the wave
         const int lane_max =
             __builtin_popcountll(ballot(lit > 16)) >= kLaneRunMin ? kLaneRun : 16;
+        ECOUNT(0, __builtin_popcountll(ballot(lit > 0 && lit <= lane_max)));
         if constexpr (kRuns) {
             lane_runs(D, lsrc, S, lp, lit, lit > 0 && lit <= lane_max);
         } else {
@@ -456,16 +504,213 @@ __device__ __forceinline__ int emit_sequences(const lds8* D, const Em& em, const
             for (int d0 = 0; ballot(mine && d0 < lit) != 0; d0 += 16)
                 if (mine && d0 < lit) lane_copy16(D, lsrc + d0, S, lp + d0, min(16, lit - d0));
         }
+        ESTAMP(2);
         for (uint64_t lm = ballot(lit > lane_max); lm; lm &= lm - 1) {
             const int l = ffs64(lm);
+            ECOUNT(1, 1);
+            ECOUNT(2, (__builtin_amdgcn_readlane(lit, l) / 4 + kWave - 1) / kWave);
             wave_copy(D, __builtin_amdgcn_readlane(lsrc, l), S, __builtin_amdgcn_readlane(lp, l),
                       __builtin_amdgcn_readlane(lit, l), lane);
         }
+        ESTAMP(3);
         if (m) {
             S[lp + lit] = (uint8_t)(off & 0xFF);
             S[lp + lit + 1] = (uint8_t)(off >> 8);
         }
         lane_len_run(S, lp + lit + 2, me, (uint32_t)(mc - 15) % 255u);
+        ESTAMP(1);
+    }
+    return opb - 4;
+}
+
+// lane_runs_interior with two steps of reads in flight instead of one, fully
+// unrolled over the kFlatLaneRun / 16 steps a per-lane run can take, so that every
+// source dword has a register of its own: a rotating pipeline's register
+// copies at the loop's end wait for the reads they move (the compiler puts
+// s_waitcnt lgkmcnt(0) in front of them), which is a round trip per step
+// again.  The reads are unmasked -- every lane's W points into the block, and
+// a lane whose run is shorter than the batch's longest over-reads at most
+// 40 bytes past it, into the readable LDS behind the block -- so
+// only the writes toggle the exec mask.  A step is skipped, with all later
+// ones, once no lane has a dword left.
+constexpr int kLaneSteps = kFlatLaneRun / 16;  // interior dwords 1 .. (kFlatLaneRun + 6) / 4 - 2 <= 4 * kLaneSteps
+static_assert(kFlatLaneRun % 16 == 0 && (kFlatLaneRun + 6) / 4 - 2 <= 4 * kLaneSteps, "steps of four dwords");
+__device__ __forceinline__ void lane_runs_deep(const lds32* W, lds32* O, const uint32_t r, const int last) {
+    if (ballot(1 <= last) == 0) return;
+    uint32_t w[4 * kLaneSteps + 2];
+#pragma unroll
+    for (int i = 1; i <= 9; i++) w[i] = W[i];
+#pragma unroll
+    for (int s = 0; s < kLaneSteps; s++) {
+        const int t = 1 + 4 * s;
+        const bool more = s + 1 < kLaneSteps && ballot(t + 4 <= last) != 0;
+        if (s + 2 < kLaneSteps && more) {
+#pragma unroll
+            for (int i = t + 9; i <= t + 12; i++) w[i] = W[i];
+        }
+        if (t <= last) {
+            O[t] = __builtin_amdgcn_alignbyte(w[t + 1], w[t], r);
+            if (t + 1 <= last) O[t + 1] = __builtin_amdgcn_alignbyte(w[t + 2], w[t + 1], r);
+            if (t + 2 <= last) O[t + 2] = __builtin_amdgcn_alignbyte(w[t + 3], w[t + 2], r);
+            if (t + 3 <= last) O[t + 3] = __builtin_amdgcn_alignbyte(w[t + 4], w[t + 3], r);
+        }
+        if (!more) break;
+    }
+}
+
+// The wave's literal runs: the interior destination dwords (1 .. nd - 2) of
+// every run whose lane is in `lm`, run after run.  Source base, destination
+// base and shift are the run's, read from its lane with v_readlane, so no lane
+// searches for its run.  What the phase costs is its LDS wave-instructions (a
+// CU's six waves queue on one LDS; profiles/enc_chain), so a run takes as few
+// as its size allows:
+//  * up to 64 interior dwords: one dword per lane, one read pair and one write;
+//  * longer: 16-byte chunks of the DESTINATION, one per lane and step -- two
+//    aligned 16-byte reads (the chunk's five source dwords lie in two aligned
+//    16-byte granules, at the same dword q of the first for every lane), four
+//    v_alignbyte, one 16-byte write; the <= 3 dwords in front of the first
+//    chunk and behind the last go in one step of their own (lanes 0-3, 4-7).
+// Reads are unmasked: a step over-reads at most 64 chunks past the run, into
+// the >= 2 KiB of readable LDS behind the block.  b: the source byte of
+// destination dword 0's byte 0, dpa: destination dword 0 (4-aligned), nd:
+// destination dwords touched; every run in lm has nd >= 3.
+static_assert(kWave * 16 + 48 <= kDescBytes, "a chunk step over-reads into the descriptors only");
+__device__ __forceinline__ void wave_runs(const lds8* D, lds8* S, uint64_t lm, int b, int dpa, int nd,
+                                          int lane, EmitDiag& ed) {
+    (void)ed;
+    for (; lm; lm &= lm - 1) {
+        const int l = ffs64(lm);
+        const int bl = __builtin_amdgcn_readlane(b, l);
+        const uint32_t w = (uint32_t)(uintptr_t)(D + (bl & ~3));
+        const uint32_t o = (uint32_t)(uintptr_t)(S + __builtin_amdgcn_readlane(dpa, l));
+        const uint32_t r = (uint32_t)(bl & 3);
+        const int last = __builtin_amdgcn_readlane(nd, l) - 2;
+        const lds32* W = (const lds32*)(uintptr_t)w;
+        lds32* O = (lds32*)(uintptr_t)o;
+        ECOUNT(1, 1);
+        ECOUNT(2, 1);
+        if (last <= kWave) {
+            const int t = 1 + lane;
+            const uint32_t x0 = W[t], x1 = W[t + 1];
+            if (t <= last) O[t] = __builtin_amdgcn_alignbyte(x1, x0, r);
+            continue;
+        }
+        const int a = 1 + (int)(((0u - (o + 4u)) & 15u) >> 2);  // first dword on a 16-byte destination
+        const int nc = (last - a + 1) >> 2;                      // whole chunks
+        {
+            const int te = lane < 4 ? 1 + lane : a + 4 * nc + (lane - 4);
+            const bool on = lane < 4 ? te < a : (lane < 8 && te <= last);
+            const int t = on ? te : 1;
+            const uint32_t x0 = W[t], x1 = W[t + 1];
+            if (on) O[t] = __builtin_amdgcn_alignbyte(x1, x0, r);
+        }
+        const uint32_t sa = w + 4u * (uint32_t)a;
+        const uint32_t q = (sa >> 2) & 3u;
+        const lds128* X = (const lds128*)(uintptr_t)(sa & ~15u);
+        lds128* Oc = (lds128*)(uintptr_t)(o + 4u * (uint32_t)a);
+        for (int c0 = 0; c0 < nc; c0 += kWave) {
+            ECOUNT(2, 1);
+            const int c = c0 + lane;
+            const u32x4 x = X[c], y = X[c + 1];
+            u32x4 v;
+            auto ab = [&](uint32_t hi, uint32_t lo) { return __builtin_amdgcn_alignbyte(hi, lo, r); };
+            if (q == 0)
+                v = u32x4{ab(x.y, x.x), ab(x.z, x.y), ab(x.w, x.z), ab(y.x, x.w)};
+            else if (q == 1)
+                v = u32x4{ab(x.z, x.y), ab(x.w, x.z), ab(y.x, x.w), ab(y.y, y.x)};
+            else if (q == 2)
+                v = u32x4{ab(x.w, x.z), ab(y.x, x.w), ab(y.y, y.x), ab(y.z, y.y)};
+            else
+                v = u32x4{ab(y.x, x.w), ab(y.y, y.x), ab(y.z, y.y), ab(y.w, y.z)};
+            if (c < nc) Oc[c] = v;
+        }
+    }
+}
+
+// emit_sequences with as few LDS wave-instructions and dependent LDS stages as
+// the data allows (the default; A/B bit 4194304 off: the emitter above).  Per
+// batch of 64 sequences: the descriptor read and the prefix sum; then the head
+// and tail source dwords of every literal run are requested, and while they
+// travel the token, offset and length bytes go out as masked dwords
+// (lane_put5; length runs in closed form, no loop over their bytes); the
+// heads and tails land as masked dwords; runs up to kFlatLaneRun bytes copy
+// their interior dwords themselves (lane_runs_deep), and all longer runs go by
+// the wave (wave_runs), 16 bytes per lane and step where the run is long
+// enough.  Block and record are disjoint LDS, so nothing waits except a read's
+// own use.
+template <class Em>
+__device__ __forceinline__ int emit_sequences_flat(const lds8* D, const Em& em, const int n, lds8* S,
+                                                   const int lane, EmitDiag& ed) {
+    (void)ed;
+    const int ns = em.ns, la = em.la;
+    int opb = 4;
+    ESTART;
+    for (int b0 = 0; b0 <= ns; b0 += kWave) {
+        const int s = b0 + lane;
+        const bool m = s < ns;
+        const bool act = s <= ns;
+        int ip = n, off = 0, lit = act ? n - la : 0, mc = 0;
+        if (m) {
+            const u32x2 d = ((const lds64v*)em.desc)[s];
+            const uint32_t x = d.x, y = d.y;
+            ip = (int)(x & 0xFFFFu);
+            off = (int)(x >> 16);
+            lit = (int)(y & 0xFFFFu);
+            mc = (int)(y >> 16) - kMinMatch;
+        }
+        const int le = lz4_ext_bytes(lit), me = m ? lz4_ext_bytes(mc) : 0;
+        const int len = act ? 1 + le + lit + (m ? 2 + me : 0) : 0;
+        const int incl = wave_incl_sum(len, lane);
+        const int op = opb + incl - len;
+        opb += __builtin_amdgcn_readlane(incl, kWave - 1);
+        const int lp = op + 1 + le, lsrc = ip - lit;
+        // the run in destination dwords: dword t of the nd it touches is
+        // v_alignbyte(W[t + 1], W[t], r), one shift for the whole run
+        const int k = lp & 3;
+        const int b = lsrc - k;  // may be < 0 (k bytes in front of the block: masked off)
+        const uint32_t r = (uint32_t)(b & 3);
+        const lds32* W = (const lds32*)(D + (b & ~3));
+        lds32* O = (lds32*)(S + (lp & ~3));
+        const int nd = ((lp + lit + 3) >> 2) - (lp >> 2);
+        const bool has = lit > 0;
+        uint32_t h0 = 0, h1 = 0, t0 = 0, t1 = 0;
+        if (has) {
+            h0 = W[0];
+            h1 = W[1];
+            t0 = W[nd - 1];
+            t1 = W[nd];
+        }
+        ESTAMP(0);
+        // token + the first four literal-length bytes, and offset + the first
+        // three match-length bytes: two masked dwords each, every lane (a
+        // lane without a sequence writes under an empty mask)
+        const uint32_t ll = (uint32_t)(lit - 15) % 255u, ml = (uint32_t)(mc - 15) % 255u;
+        lane_put5(S, op, (uint64_t)(uint32_t)((min(lit, 15) << 4) | (m ? min(mc, 15) : 0)) |
+                             (uint64_t)len_run_head<4>(le, ll) << 8,
+                  act ? 1 + min(le, 4) : 0);
+        lane_put5(S, lp + lit, (uint64_t)(uint32_t)off | (uint64_t)len_run_head<3>(me, ml) << 16,
+                  m ? 2 + min(me, 3) : 0);
+        lane_len_rest<4>(S, op + 1, le, ll, lane);
+        lane_len_rest<3>(S, lp + lit + 2, me, ml, lane);
+        ECOUNT(3, __builtin_popcountll(ballot(le > 4)) + __builtin_popcountll(ballot(me > 3)));
+        ESTAMP(1);
+        if (has) {
+            const int e = lp + lit - 4 * ((lp + lit - 1) >> 2);  // bytes of the run in its last dword, 1..4
+            const uint32_t mt = e >= 4 ? ~0u : ((1u << (8 * e)) - 1u);
+            uint32_t mh = ~0u << (8 * k);
+            if (nd == 1) mh &= mt;
+            lds_write_masked(lds_addr((lds8*)O), mh, __builtin_amdgcn_alignbyte(h1, h0, r) & mh);
+            if (nd > 1)
+                lds_write_masked(lds_addr((lds8*)(O + nd - 1)), mt, __builtin_amdgcn_alignbyte(t1, t0, r) & mt);
+        }
+        const int lane_max =
+            __builtin_popcountll(ballot(lit > 16)) >= kLaneRunMin ? kFlatLaneRun : 16;
+        const bool mine = has && lit <= lane_max;
+        ECOUNT(0, __builtin_popcountll(ballot(mine)));
+        lane_runs_deep(W, O, r, mine ? nd - 2 : 0);
+        ESTAMP(2);
+        wave_runs(D, S, ballot(lit > lane_max), b, lp & ~3, nd, lane, ed);
+        ESTAMP(3);
     }
     return opb - 4;
 }
@@ -1959,6 +2204,11 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
     // stays in the table's LDS until the next block is transposed.
     constexpr bool kDefer = (EK != 0 || BSHUF_EK0_DEFER) && (VAR & 4096) == 0;
     constexpr bool kFlush4 = BSHUF_FLUSH4 && EK != 4;
+    // kFlush4 reads whole groups of 4 x 64 chunks without a bound, and the
+    // emission stages a record only when 4 + lz4_bound(n) + 15 <= kTableBytes:
+    // the largest staged record and the reads past it stay inside the table
+    static_assert(kTableBytes % (4 * kWave * 16) == 0 && kTableBytes / 16 == 1024,
+                  "kFlush4's unbounded chunk reads assume a 16 KiB staging area");
     int64_t pend_blk = -1;
     int pend_c = 0;
     auto flush_pending = [&]() {
@@ -2141,7 +2391,10 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     lds8* S = L0;
-                    c = emit_sequences<(VAR & 2097152) != 0>(D, em, n, S, lane);
+                    if constexpr ((VAR & kVarEmitFlat) != 0)
+                        c = emit_sequences_flat(D, em, n, S, lane, KEMITDIAG);
+                    else
+                        c = emit_sequences<(VAR & 2097152) != 0>(D, em, n, S, lane, KEMITDIAG);
                     if (lane < 4) S[lane] = (uint8_t)((uint32_t)c >> (24 - 8 * lane));
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
@@ -2468,7 +2721,12 @@ hipError_t launch_enc_t(const EncArgs& a, int64_t nb, size_t lds, hipStream_t s)
         // 1.036, E = 12 1.129 -> 1.001 per launch (profiles/r05/r5d; lane_runs
         // alone -0.3..-0.6 % of that); 450560 / 172032, 319488 / 40960 stay as
         // A/B variants
-        if (v == 0) return launch_enc_t<EK, WIDE, VAR | (EK == 0 ? 2793472 : 3072000)>(a, nb, lds, s);
+        // ... and the emission with closed-form length runs and one pipelined
+        // wave pass over the long literal runs (emit_sequences_flat, | 4194304;
+        // the numbers: DESIGN.md 6.5, profiles/enc_chain); 3072000 / 2793472,
+        // round 5's defaults, stay as A/B variants
+        if (v == 0)
+            return launch_enc_t<EK, WIDE, VAR | kVarEmitFlat | (EK == 0 ? 2793472 : 3072000)>(a, nb, lds, s);
         if (v == 3072000 && EK != 0) return launch_enc_t<EK, WIDE, VAR | 3072000>(a, nb, lds, s);
         if (v == 3072000 || v == 2793472) return launch_enc_t<EK, WIDE, VAR | 2793472>(a, nb, lds, s);
         if (v == 40960) return launch_enc_t<EK, WIDE, VAR | 40960>(a, nb, lds, s);

@@ -223,9 +223,10 @@ int bshuf_set_variant(int v) {
     // 24576 both, 57344 both with the shortcut (319488: + bit-sliced forward transpose), 40960 the re-test chain with its offset-2 shortcut (the
     // default for byU16 blocks), 65536 the compiled re-test chain, 172032 /
     // 450560 the 40960 / 319488 ones with the search-match hand-off in asm
-    // (search_entry), 2793472 / 3072000 (the defaults) those with the whole
+    // (search_entry), 2793472 / 3072000 those with the whole
     // parse loop as one asm block (parse_chain) and the emission's literal
-    // runs by lane_runs; any of
+    // runs by lane_runs -- round 5's defaults; today's add the flat emission
+    // (emit_sequences_flat), which has no value of its own: 0 selects it; any of
     // them | kNoPipe (1 << 20): no pipelined encode, | kStaticSched (1 << 24) /
     // kTicketSched (1 << 25): static / ticket block assignment in both
     // persistent kernels, | kNoSteal (1 << 26): a wave leaves when its own

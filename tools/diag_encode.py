@@ -1,7 +1,7 @@
 """Phase split of k_lz4_encode from the diagnostic build (BSHUF_DIAG stamps).
 Usage: python tools/diag_encode.py [GiB] [gen] [elem_size] [variant]   (runs on the GPU box;
 variant 16777216 = static block assignment, 67108864 = no stealing between
-ticket shards).  BSHUF_DIAG_SKEW=s: noise in the blocks = s (mod 8), zeros
+ticket shards, 3072000 = round 5's emission).  BSHUF_DIAG_SKEW=s: noise in the blocks = s (mod 8), zeros
 elsewhere.  Ends with the per-shard finish table of the call's parse launches."""
 import ctypes
 import os
@@ -80,7 +80,7 @@ v = list(buf)
 names = ["search", "catch+count", "(unused)", "seq-record", "retest", "last"]
 cnt = ["matches", "windows", "collision_windows", "retest_hits", "blocks", "literal_bytes",
        "searches"]
-blocks = max(v[12], 1)
+blocks = max(v[12] or v[22], 1)  # the asm parse does not count blocks: the waves' sum
 tot = sum(v[:6])
 print("blocks", blocks, "ratio", x.numel() * x.element_size() / c.numel())
 for i, nm in enumerate(names):
@@ -90,6 +90,14 @@ kn = ["zero+transpose", "parse", "emit+copy-out", "loop/other"]
 ktot = sum(v[16:20])
 for i, nm in enumerate(kn):
     print("kernel %-15s %8.0f cyc/block  %5.1f%%" % (nm, v[16 + i] / blocks, 100.0 * v[16 + i] / max(ktot, 1)))
+# the emission's sub-phases (each stamp drains the LDS queue, so they add up
+# to more than the product build's emission) and events
+en = ["desc+prefix", "token/len/offset", "lane runs", "wave runs"]
+for i, nm in enumerate(en):
+    print("emit %-17s %8.0f cyc/block  %5.1f%% of emit+copy-out" % (nm, v[24 + i] / blocks, 100.0 * v[24 + i] / max(v[18], 1)))
+ec = ["runs_per_lane", "runs_by_wave", "wave_copy_steps", "len_run_steps"]
+for i, nm in enumerate(ec):
+    print("%-18s %8.2f per block" % (nm, v[28 + i] / blocks))
 for i, nm in enumerate(cnt):
     print("%-18s %8.2f per block" % (nm, v[8 + i] / blocks))
 # blocks per wave over the call's parse launches: equal under the static
