@@ -25,6 +25,7 @@
 
 #include <cstdlib>
 
+#include "inplace.h"
 #include "launch.h"
 #include "lds_copy.h"
 #include "lz4_scan.h"
@@ -875,7 +876,7 @@ __device__ __forceinline__ int span_shift(const DecArgs& a, const Span& sp) {
     return (int)((uintptr_t)(sp.loc.in + sp.o0) & 15);
 }
 __device__ __forceinline__ int span_chunks(const DecArgs& a, const Span& sp) {
-    return (span_shift(a, sp) + (int)(sp.o1 - sp.o0) + 15) >> 4;
+    return span_granules(span_shift(a, sp), (int)(sp.o1 - sp.o0));
 }
 
 __device__ __forceinline__ bool span_fits(const DecArgs& a, const Span& sp) {
@@ -1000,10 +1001,7 @@ struct GReader {
 // A quarter of the scattered position stores (each costs a whole write
 // transaction, and on gfx9's in-order vmcnt every store issued before a
 // window load is waited for with it).
-constexpr int kMxBias = 1 << 14;
-// Bytes behind the decoded block reserved for the in-place record (keeps one
-// buffer within 7 LDS granules = 8,960 bytes: 18 waves per CU)
-constexpr int kInPlaceMargin = 704;
+// (kMxBias, kInPlaceMargin and the in-place placement arithmetic: inplace.h)
 struct SeqOut {
     typedef __attribute__((address_space(1))) uint32_t g32;
     uint32_t* base;
@@ -1070,9 +1068,10 @@ __global__ __launch_bounds__(256) void k_seq_scan(DecArgs a, int64_t nb) {
         const int r = scan_block(rd, (int)clen, n, out, cnt);
         out.flush(cnt);  // a rejected block's positions are never read
         st = r < 0 ? (int64_t)r - 1000 : (r == n ? (int64_t)cnt : -91);
-        // valid: bits 32..47 carry max(output start - token position) + 2^14,
-        // the in-place decoder's safety margin test (kInPlace below)
-        if (st >= 0) st |= (int64_t)min(max(out.mx + kMxBias, 0), 0xFFFF) << 32;
+        // valid: kMxBits bits from bit 32 on carry max(output start - token
+        // position) + 2^14, the in-place decoder's safety margin test (kInPlace
+        // below; inplace.h)
+        if (st >= 0) st |= inplace_mx_pack(out.mx);
     }
     a.status[k] = st;
 }
@@ -1286,6 +1285,9 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
     // occupancy of the global-read decoder stays.
     constexpr bool kIP = (VAR & 512) != 0;
     auto cbuf_of = [&](const Span& sp) -> lds8* {
+        // (= smem + inplace_span_off(a.ip_end, span_chunks), inplace.h; written out
+        // here because that association of the pointer sum allocates registers
+        // differently)
         return kIP ? to_lds(smem) + a.ip_end - 16 * span_chunks(a, sp) : Cbuf;
     };
     int64_t blk = a.blk0 + blockIdx.x;
@@ -1373,8 +1375,8 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
                 lz4_exec_block(src, 0, D, cur.loc.seq + cur.o0 / 3, (int)cur.scan, cur_pos, lane, dg);
         } else {
             clen = (int)(((uint32_t)C[0] << 24) | ((uint32_t)C[1] << 16) | ((uint32_t)C[2] << 8) | C[3]);
-            const int mx = (int)((cur.scan >> 32) & 0xFFFF) - kMxBias;
-            if (!kIP || mx <= (int)(CB - D) + cp + 4) {
+            const int mx = inplace_mx_unpack(cur.scan);
+            if (!kIP || inplace_fits(mx, (int)(CB - D), cp)) {
                 if (!(VAR & 64))
                     lz4_exec_block<kIP, (VAR >> 10) & 3>(LdsRec{CB}, cp + 4, D, cur.loc.seq + cur.o0 / 3,
                                         (int)cur.scan, cur_pos, lane, dg);
@@ -1849,16 +1851,18 @@ hipError_t decode_impl(DecArgs& a, int64_t nb, bool aligned, hipStream_t s) {
     const bool touch = tuning_variant() == 16;
     // default: the record in place at the end of the block's own buffer
     const bool inplace = !grec && tuning_variant() != 64;
-    a.ip_end = (int32_t)(((size_t)a.cap + kInPlaceMargin + 15) & ~(size_t)15);
+    a.ip_end = inplace_end(a.cap);
     size_t lds = inplace ? (size_t)a.ip_end + 32 : (size_t)a.cap + 16 + (grec ? 0 : rec);
     const int ek = aligned && (L.E == 1 || L.E == 2 || L.E == 4 || L.E == 8) ? L.E : 0;
     // any other element size: stage the inverse transpose when every output
     // is 8-aligned (a.stage_off was set to 1 by the caller as "may") -- through
     // registers for blocks of <= 8 KiB (stage_off -1), else in an LDS block of
-    // its own
+    // its own, when that still fits the CU's 160 KiB (blocks of some 54 KiB and
+    // more with the record in a buffer of its own, the largest 168 bytes of
+    // block sizes in place: byte stores instead of a launch the runtime refuses)
     if (ek == 0 && a.stage_off && (int64_t)L.bs * L.E <= 8192) {
         a.stage_off = -1;
-    } else if (ek == 0 && a.stage_off) {
+    } else if (ek == 0 && a.stage_off && lds + (size_t)a.cap <= (size_t)160 * 1024) {
         a.stage_off = (int32_t)lds;
         lds += (size_t)a.cap;
     } else {

@@ -4,6 +4,7 @@
 // product library.
 #include <stdint.h>
 
+#include "inplace.h"
 #include "lz4_scan.h"
 #include "pipe_segments.h"
 #include "ticket_steal.h"
@@ -15,9 +16,10 @@ struct HostReader {
 };
 struct HostOut {
     uint32_t* pos;
+    int mx = -(1 << 20);  // max over sequences of (output start - token position), as SeqOut
     void put(int i, uint32_t v, int op) {
         pos[i] = v;
-        (void)op;
+        mx = mx > op - (int)v ? mx : op - (int)v;
     }
 };
 }  // namespace
@@ -30,6 +32,30 @@ extern "C" int bshuf_hostcheck_scan(const uint8_t* payload, int clen, int n, uin
     const int r = bshuf::scan_block(rd, clen, n, out, cnt);
     *nseq = cnt;
     return r;
+}
+
+// ... and the in-place decoder's margin value of the block, as k_seq_scan packs
+// it into its verdict and k_lz4_decode unpacks it (inplace.h)
+extern "C" int bshuf_hostcheck_scan_mx(const uint8_t* payload, int clen, int n, uint32_t* pos,
+                                       int* nseq, int* mx_raw, int* mx_seen) {
+    HostReader rd{payload};
+    HostOut out{pos};
+    int cnt = 0;
+    const int r = bshuf::scan_block(rd, clen, n, out, cnt);
+    *nseq = cnt;
+    *mx_raw = out.mx;
+    *mx_seen = bshuf::inplace_mx_unpack(bshuf::inplace_mx_pack(out.mx));
+    return r;
+}
+
+// inplace.h as the launcher and the kernel use it: a span of span_bytes that
+// starts `shift` bytes into a 16-byte granule, in the buffer of a block with
+// cap reserved bytes.  Returns whether the block is decoded in place.
+extern "C" int bshuf_hostcheck_inplace(int cap, int shift, int span_bytes, int mx, int* ip_end,
+                                       int* span_off) {
+    *ip_end = bshuf::inplace_end(cap);
+    *span_off = bshuf::inplace_span_off(*ip_end, bshuf::span_granules(shift, span_bytes));
+    return bshuf::inplace_fits(mx, *span_off, shift) ? 1 : 0;
 }
 
 // pipe_segments.h as the launcher uses it

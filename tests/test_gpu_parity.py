@@ -298,8 +298,10 @@ def test_decoder_crafted_sequences_match_oracle(bs, oracle, E):
     """Streams of hand-built LZ4 records (not what the encoder emits): every
     decoder match path -- per-lane and wave copies, periods 0/1/2/3/4/other,
     matches reading the previous sequence's output (batch breaks), long
-    lengths -- against the oracle's LZ4_decompress_safe restatement.  Blocks
-    whose in-place margin fails take the decoder's global-record path."""
+    lengths -- against the oracle's LZ4_decompress_safe restatement.  (Every
+    block here passes the in-place margin test: only a stream's last block
+    behind a raw tail of some 700 bytes fails it, tests/test_gpu_decode_paths.py
+    and DESIGN.md 4.1.)"""
     rng = np.random.default_rng(4242 + E)
     nbytes = 8192
     frames = bytearray()
