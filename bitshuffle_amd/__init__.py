@@ -16,6 +16,12 @@ Host (numpy) functions
 Device (torch CUDA/HIP tensor) functions, no host round trip
     bitshuffle_dev / bitunshuffle_dev / compress_lz4_dev / decompress_lz4_dev
     compress_lz4_batch_dev / decompress_lz4_batch_dev  (many streams per launch)
+Random-access decode (device): element ranges of one stream, decoding only
+the blocks they touch
+    decompress_lz4_ranges_dev(buf, size, dtype, ranges, ...) -> list of tensors,
+        one per (start, count) of `ranges`, views of one dense output
+    decompress_lz4_range_dev(buf, size, dtype, start, count, ...) -> tensor
+    decompress_lz4_ranges_workspace(in_nbytes, size, elem_size, ranges, ...)
 """
 from ._lib import (  # noqa: F401
     LIB_PATH,
@@ -40,6 +46,9 @@ from .api import (  # noqa: F401
     decompress_lz4,
     decompress_lz4_batch_dev,
     decompress_lz4_dev,
+    decompress_lz4_range_dev,
+    decompress_lz4_ranges_dev,
+    decompress_lz4_ranges_workspace,
     default_block_size,
     synth_fill_dev,
 )
@@ -64,5 +73,8 @@ __all__ = [
     "decompress_lz4_dev",
     "compress_lz4_batch_dev",
     "decompress_lz4_batch_dev",
+    "decompress_lz4_ranges_dev",
+    "decompress_lz4_range_dev",
+    "decompress_lz4_ranges_workspace",
     "FAST_PARSE_VERSION",
 ]

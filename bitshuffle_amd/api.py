@@ -251,6 +251,84 @@ def decompress_lz4_dev(buf, shape, dtype, block_size=0, out=None, workspace=None
     return out
 
 
+def _range_arrays(ranges):
+    starts, counts = [], []
+    for start, count in ranges:
+        start, count = int(start), int(count)
+        if start < 0 or count < 0:
+            raise ValueError("a range is (start, count) with both >= 0, not (%d, %d)" % (start, count))
+        starts.append(start)
+        counts.append(count)
+    ps, keep1 = _size_array(starts)
+    pc, keep2 = _size_array(counts)
+    return counts, ps, pc, (keep1, keep2)
+
+
+def decompress_lz4_ranges_workspace(in_nbytes, size, elem_size, ranges, block_size=0, device=None):
+    """A workspace for decompress_lz4_ranges_dev of these ranges (or of other
+    ranges that touch no more blocks) of a stream of `in_nbytes` bytes."""
+    torch = _torch()
+    _, ps, pc, keep = _range_arrays(ranges)
+    n = int(lib.bshuf_decompress_lz4_ranges_dev_workspace(in_nbytes, size, elem_size, block_size,
+                                                          ps, pc, len(ranges)))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device or "cuda")
+
+
+def decompress_lz4_ranges_dev(buf, size, dtype, ranges, block_size=0, out=None, workspace=None,
+                              result=None, offsets=None, stream=None, sync=True, elem_size=None):
+    """Random-access decode (bshuf_decompress_lz4_ranges_dev): the element
+    ranges `ranges` -- a sequence of (start, count) -- of the framed stream in
+    uint8 device tensor `buf`, which encodes `size` elements of `dtype`; only
+    the blocks a range touches are decoded.  The ranges' elements land back to
+    back in one dense `out`; returns one tensor per range, views of it
+    (sync=True), or (out, result) with result a 1-element int64 device tensor
+    of the byte count / error code (sync=False).  Ranges may overlap, repeat,
+    come in any order and be empty.  `offsets`: the stream's block index
+    (compress_lz4_dev's `offsets=` tensor, or block_index_dev's); without it
+    the index is rebuilt from the whole stream.  With `elem_size`, size, start
+    and count are in elem_size-byte elements and the output is uint8."""
+    torch = _torch()
+    ranges = list(ranges)
+    counts, ps, pc, keep = _range_arrays(ranges)
+    total = sum(counts)
+    if out is None:
+        if elem_size is None:
+            out = torch.empty(total, dtype=dtype, device=buf.device)
+        else:
+            out = torch.empty(total * int(elem_size), dtype=torch.uint8, device=buf.device)
+    es = out.element_size() if elem_size is None else int(elem_size)
+    if out.numel() * out.element_size() < total * es:
+        raise ValueError("out holds %d bytes, the ranges need %d"
+                         % (out.numel() * out.element_size(), total * es))
+    if result is None:
+        result = torch.empty(1, dtype=torch.int64, device=buf.device)
+    ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+    wsb = workspace.numel() if workspace is not None else 0
+    offp = _dptr(offsets) if offsets is not None else None
+    _check(lib.bshuf_decompress_lz4_ranges_dev(_dptr(buf), buf.numel(), int(size), es, block_size,
+                                               ps, pc, len(ranges), _dptr(out), ws, wsb,
+                                               _dptr(result), offp, _stream(stream)))
+    if not sync:
+        return out, result
+    count = int(result.item())
+    if count < 0:
+        _fail(count)
+    per = 1 if elem_size is None else es  # out items per element
+    flat = out.reshape(-1)
+    views, at = [], 0
+    for c in counts:
+        views.append(flat[at * per:(at + c) * per])
+        at += c
+    return views
+
+
+def decompress_lz4_range_dev(buf, size, dtype, start, count, **kw):
+    """One range of decompress_lz4_ranges_dev: the tensor of elements
+    [start, start + count) (sync=True), or (out, result) (sync=False)."""
+    r = decompress_lz4_ranges_dev(buf, size, dtype, [(start, count)], **kw)
+    return r if kw.get("sync", True) is False else r[0]
+
+
 def block_index_dev(buf, size, elem_size, block_size=0, workspace=None, stream=None):
     """The block index of the framed stream in uint8 device tensor `buf` for
     `size` elements of `elem_size` bytes (bshuf_lz4_block_index_dev, the

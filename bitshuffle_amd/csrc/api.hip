@@ -16,6 +16,7 @@
 #include "../../include/bitshuffle.h"
 #include "launch.h"
 #include "plan.h"
+#include "range_plan.h"
 
 using namespace bshuf;
 
@@ -609,6 +610,281 @@ int64_t bshuf_decompress_lz4_batch_dev_dlen(const void* const* in, const int64_t
     if (!d_in_nbytes) return kErrUnsupported;
     return decompress_batch(in, in_capacity, d_in_nbytes, out, sizes, count, elem_size, block_size,
                             ws, ws_bytes, d_results, stream);
+}
+
+// ---------------------------------------------------------------------------
+// element ranges of one stream
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// The pieces of every range of a call (range_plan.h), before they have
+// addresses: decode pieces (interior blocks, edge blocks) and tail spans.
+struct ProtoPiece {
+    int kind;
+    int64_t b0, nblk;  // decode pieces: blocks of the stream
+    int64_t nfull;     // ... of which full ones
+    int32_t last;      // ... and the elements of the stream's partial block, when it is one of them
+    int64_t dst;       // byte offset in the output (interior, clip, tail span)
+    int64_t lo, n;     // edge: clip bytes of the staging block; tail span: bytes of the tail
+    int64_t slot;      // edge: its staging block
+};
+
+struct RangePlan {
+    std::vector<ProtoPiece> dec, tails;
+    int64_t nblk = 0;       // work blocks (every decode piece's)
+    int64_t nedge = 0;      // staging blocks
+    int64_t max_blk = 0;    // most blocks / elements of one piece (large blocks: one piece at a time)
+    int64_t max_elems = 0;
+    int64_t seq_words = 0;  // token positions: a private area per piece, or (shared_seq) the
+    bool shared_seq = false;  // whole decode's area indexed by stream offset, when that is smaller
+    int64_t total = 0;      // output bytes
+    bool large = false;
+};
+
+int64_t plan_ranges(const Plan& p, size_t size, size_t in_nbytes, const size_t* starts,
+                    const size_t* counts, size_t nranges, RangePlan& rp) {
+    if (nranges > (size_t)INT32_MAX / 4) return kErrUnsupported;
+    const Layout& L = p.L;
+    const int64_t E = L.E, maxlen = lz4_bound(L.bs * L.E);
+    int64_t private_words = 0;
+    auto add_dec = [&](int kind, int64_t b0, int64_t b1, int64_t dst, int64_t lo, int64_t n) {
+        ProtoPiece q{};
+        q.kind = kind;
+        q.b0 = b0;
+        q.nblk = b1 - b0;
+        q.nfull = std::min(b1, L.nfull) - b0;
+        q.last = b1 > L.nfull ? L.last : 0;
+        q.dst = dst;
+        q.lo = lo;
+        q.n = n;
+        q.slot = kind == kPieceEdge ? rp.nedge++ : 0;
+        rp.nblk += q.nblk;
+        rp.max_blk = std::max(rp.max_blk, q.nblk);
+        rp.max_elems = std::max(rp.max_elems, q.nfull * L.bs + q.last);
+        private_words += q.nblk * (4 + maxlen) / 3 + 80;
+        rp.dec.push_back(q);
+    };
+    for (size_t i = 0; i < nranges; i++) {
+        if (starts[i] > size || counts[i] > size - starts[i]) return kErrUnsupported;
+        RangePieces r;
+        range_pieces((int64_t)size, L.bs, E, (int64_t)starts[i], (int64_t)counts[i], rp.total, r);
+        rp.total += (int64_t)counts[i] * E;
+        if (r.b1 > r.b0) add_dec(kPieceInterior, r.b0, r.b1, r.int_dst, 0, 0);
+        for (const RangeEdge* e : {&r.head, &r.tail})
+            if (e->hi > e->lo) add_dec(kPieceEdge, e->blk, e->blk + 1, e->dst, e->lo * E, (e->hi - e->lo) * E);
+        if (r.tail_n > 0) {
+            ProtoPiece q{};
+            q.kind = kPieceTail;
+            q.dst = r.tail_dst;
+            q.lo = r.tail_lo * E;
+            q.n = r.tail_n * E;
+            rp.tails.push_back(q);
+        }
+    }
+    if (rp.nblk >= ((int64_t)1 << 31)) return kErrUnsupported;
+    rp.large = (int64_t)L.bs * L.E > max_lds_decode_bytes();
+    const int64_t shared_words = (int64_t)in_nbytes / 3 + 80;
+    rp.shared_seq = rp.large || shared_words < private_words;
+    rp.seq_words = rp.shared_seq ? shared_words : private_words;
+    return 0;
+}
+
+struct RangeBufs {
+    Seg* segs;          // one per decode piece; behind them (16-aligned) the RangePiece table
+    RangePiece* pcs;
+    size_t tab_bytes;   // ... both, as uploaded
+    uint32_t* blk_seg;
+    DecodeBufs d;       // offs: the work list; idx_err: zeros, one per decode piece
+    int64_t* res;       // one per piece
+    uint8_t* slots;     // staging blocks
+    int64_t slot;       // bytes of one
+    DecodeBufs idx;     // index rebuild of the whole stream (offs: its block index)
+};
+
+// (the index rebuild's buffers are carved whether or not the caller supplies an
+// index: one size per call shape)
+size_t range_ws(const Plan& p, const RangePlan& rp, int64_t blocks_end, RangeBufs* b, uint8_t* base) {
+    Carver c{base};
+    RangeBufs x{};
+    const size_t nd = rp.dec.size(), np = nd + rp.tails.size();
+    const size_t seg_bytes = (nd * sizeof(Seg) + 15) & ~(size_t)15;
+    x.tab_bytes = seg_bytes + np * sizeof(RangePiece);
+    x.segs = c.take<Seg>(x.tab_bytes);
+    x.pcs = reinterpret_cast<RangePiece*>(base ? reinterpret_cast<uint8_t*>(x.segs) + seg_bytes : nullptr);
+    const int64_t nwork = rp.large ? rp.max_blk : rp.nblk;
+    x.blk_seg = c.take<uint32_t>((size_t)nwork * 4 + 4);
+    x.d.offs = c.take<uint64_t>((size_t)nwork * 8 + 8);
+    x.d.status = c.take<int64_t>((size_t)nwork * 8 + 8);
+    x.d.seq = c.take<uint32_t>((size_t)rp.seq_words * 4);
+    x.d.idx_err = c.take<int64_t>(nd * 8 + 8);
+    x.d.bad = c.take<long long>(nd * 8 + 8);
+    x.d.tickets = c.take<uint32_t>(kTicketSetBytes);
+    if (rp.large) x.d.shuf = c.take<uint8_t>((size_t)rp.max_elems * p.L.E + 64);
+    x.res = c.take<int64_t>(np * 8 + 8);
+    x.slot = ((int64_t)p.L.bs * p.L.E + 15) & ~(int64_t)15;
+    x.slots = c.take<uint8_t>((size_t)(rp.nedge * x.slot));
+    {
+        x.idx.chunk = index_chunk_bytes(p.L);
+        x.idx.nchunks = blocks_end > 0 ? (blocks_end + x.idx.chunk - 1) / x.idx.chunk : 0;
+        x.idx.offs = c.take<uint64_t>((size_t)p.nb * 8 + 8);
+        x.idx.exits = c.take<int64_t>((size_t)x.idx.nchunks * 8 + 8);
+        x.idx.cnt = c.take<uint64_t>((size_t)(x.idx.nchunks + 1) * 8);
+        x.idx.base = c.take<uint64_t>((size_t)(x.idx.nchunks + 1) * 8);
+        x.idx.idx_err = c.take<int64_t>(8);
+        x.idx.scan_tmp_bytes = decode_scan_tmp_bytes(x.idx.nchunks);
+        x.idx.scan_tmp = c.take<void>(x.idx.scan_tmp_bytes + 8);
+    }
+    if (b) *b = x;
+    return c.off;
+}
+
+}  // namespace
+
+size_t bshuf_decompress_lz4_ranges_dev_workspace(size_t in_nbytes, size_t size, size_t elem_size,
+                                                 size_t block_size, const size_t* starts,
+                                                 const size_t* counts, size_t nranges) {
+    Plan p;
+    RangePlan rp;
+    if (make_plan(size, elem_size, block_size, p) ||
+        plan_ranges(p, size, in_nbytes, starts, counts, nranges, rp))
+        return 0;
+    const int64_t cb = (int64_t)in_nbytes - p.tail;
+    return range_ws(p, rp, cb > 0 ? cb : 0, nullptr, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_ranges_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                        size_t block_size, const size_t* starts, const size_t* counts,
+                                        size_t nranges, void* out, void* ws, size_t ws_bytes,
+                                        int64_t* d_result, const uint64_t* block_offsets, void* stream) {
+    Plan p;
+    int64_t r = make_plan(size, elem_size, block_size, p);
+    if (r) return r;
+    RangePlan rp;
+    r = plan_ranges(p, size, in_nbytes, starts, counts, nranges, rp);
+    if (r) return r;
+    if (!have_device()) return kErrHip;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nd = rp.dec.size(), np = nd + rp.tails.size();
+    if (np == 0) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
+    int64_t cb = (int64_t)in_nbytes - p.tail;
+    if (cb < 0) cb = 0;
+    const bool need_index = block_offsets == nullptr;
+    const size_t need = range_ws(p, rp, cb, nullptr, nullptr);
+    DevBuf own;
+    r = get_ws(ws, ws_bytes, need, own, s);
+    if (r) return r;
+    RangeBufs b;
+    range_ws(p, rp, cb, &b, (uint8_t*)ws);
+    const uint8_t* i8 = (const uint8_t*)in;
+    uint8_t* o8 = (uint8_t*)out;
+
+    // addresses: the decode pieces whose destination is 16-byte aligned first
+    // (every edge's staging block is), then the others: the aligned kernel
+    // instantiations for the former, the byte-store path for the latter
+    std::vector<uint8_t> tab(b.tab_bytes);
+    Seg* hsegs = reinterpret_cast<Seg*>(tab.data());
+    RangePiece* hpcs = reinterpret_cast<RangePiece*>(tab.data() + ((uint8_t*)b.pcs - (uint8_t*)b.segs));
+    auto where = [&](const ProtoPiece& q) {
+        return q.kind == kPieceEdge ? b.slots + q.slot * b.slot : o8 + q.dst;
+    };
+    size_t at = 0;
+    int na = 0;
+    int64_t nblk_a = 0, seq_at = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        int64_t first = 0;
+        for (const ProtoPiece& q : rp.dec) {
+            uint8_t* dst = where(q);
+            if ((((uintptr_t)dst & 15) != 0) != (pass == 1)) continue;
+            Seg& g = hsegs[at];
+            g = Seg{};
+            g.in = i8;
+            g.out = dst;
+            g.first = first;
+            g.nfull = q.nfull;
+            g.last = q.last;
+            g.in_nbytes = (int64_t)in_nbytes;
+            g.result = b.res + at;
+            RangePiece& pc = hpcs[at];
+            pc = RangePiece{};
+            pc.b0 = q.b0;
+            pc.nblk = q.nblk;
+            pc.seq_base = rp.shared_seq ? -1 : seq_at;
+            pc.src = dst + q.lo;
+            pc.dst = o8 + q.dst;
+            pc.n = q.n;
+            pc.kind = q.kind;
+            seq_at += q.nblk * (4 + (int64_t)lz4_bound(p.L.bs * p.L.E)) / 3 + 80;
+            first += q.nblk;
+            at++;
+        }
+        if (pass == 0) {
+            na = (int)at;
+            nblk_a = first;
+        }
+    }
+    for (const ProtoPiece& q : rp.tails) {
+        RangePiece& pc = hpcs[at++];
+        pc = RangePiece{};
+        pc.seq_base = -1;
+        pc.dst = o8 + q.dst;
+        pc.lo = q.lo;
+        pc.n = q.n;
+        pc.kind = kPieceTail;
+    }
+    if (stage_upload(tab.data(), tab.size(), b.segs, s) != hipSuccess) return kErrHip;
+
+    const uint64_t* offs = block_offsets;
+    const int64_t* idx_err = nullptr;
+    if (need_index) {
+        if (launch_index(i8, cb, p.L, b.idx, s, nullptr, (int64_t)in_nbytes, p.tail) != hipSuccess)
+            return kErrHip;
+        offs = b.idx.offs;
+        idx_err = b.idx.idx_err;
+    }
+    const RangeStream st{i8, (int64_t)in_nbytes, offs, p.nb, p.tail, (uint32_t)lz4_bound(p.L.bs * p.L.E)};
+    if (rp.large) {
+        // blocks above the LDS decoder's size: one piece at a time through the
+        // whole decode's route, its index being the stream's from block b0 on
+        for (size_t i = 0; i < nd; i++) {
+            Layout L = p.L;
+            L.nfull = hsegs[i].nfull;
+            L.last = hsegs[i].last;
+            DecodeBufs d = b.d;
+            d.offs = const_cast<uint64_t*>(offs) + hpcs[i].b0;
+            d.idx_err = nullptr;
+            if (launch_decode(i8, (int64_t)in_nbytes, hsegs[i].out, L, 0, d, b.res + i, s) != hipSuccess)
+                return kErrHip;
+        }
+    } else if (nd) {
+        if (dev_fill(b.d.idx_err, 0, nd * 8, s) != hipSuccess ||
+            launch_range_worklist(st, b.segs, b.pcs, (int)nd, na, nblk_a, rp.max_blk, b.d.offs, s) != hipSuccess)
+            return kErrHip;
+        // one scan + decode launch over every 16-byte aligned piece of every
+        // range, one over the others
+        const int ng[2] = {na, (int)nd - na};
+        const int64_t nbk[2] = {nblk_a, rp.nblk - nblk_a};
+        for (int g = 0; g < 2; g++) {
+            if (ng[g] == 0) continue;
+            const int s0 = g ? na : 0;
+            const int64_t k0 = g ? nblk_a : 0;
+            Layout L = p.L;
+            L.nfull = nbk[g];
+            L.last = 0;
+            DecodeBufs d = b.d;
+            d.offs += k0;
+            d.status += k0;
+            d.idx_err += s0;
+            d.bad += s0;
+            if (launch_seg_map(b.segs + s0, ng[g], b.blk_seg + k0, false, s) != hipSuccess ||
+                launch_decode_batch(b.segs + s0, hsegs + s0, ng[g], b.blk_seg + k0, L, d, s) != hipSuccess)
+                return kErrHip;
+        }
+    }
+    if (launch_range_edges(st, b.pcs, b.res, (int)np, s) != hipSuccess ||
+        launch_range_reduce(b.res, (int)np, idx_err, rp.total, d_result, s) != hipSuccess)
+        return kErrHip;
+    return 0;
 }
 
 int64_t bshuf_synth_fill_dev(void* out, size_t n_elem, int gen, uint64_t first, uint64_t seed,

@@ -239,6 +239,55 @@ hipError_t launch_decode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
 // the readable bytes of dlens[i]; run before the index rebuild
 hipError_t launch_seg_dlen(Seg* segs, const int64_t* dlens, int nsegs, hipStream_t s);
 
+// ---- range decode (lz4_range.hip) ---------------------------------------
+// Element ranges of ONE stream (bshuf_decompress_lz4_ranges_dev): every range
+// is cut into pieces (range_plan.h).  A decode piece -- interior blocks, or one
+// edge block -- is a Seg of the batch decoder whose input is the stream itself:
+// its blocks [b0, b0 + nblk) go to their place in the output (interior) or to a
+// staging block of the workspace (edge).  k_range_worklist gathers the
+// pieces' header offsets from the stream's index into the work list the batch
+// decoder reads as its offs[], k_range_edges copies every edge block's clip
+// and every tail span to the output, k_range_reduce makes the call's result.
+enum RangePieceKind { kPieceInterior = 0, kPieceEdge = 1, kPieceTail = 2 };
+struct RangePiece {
+    int64_t b0;          // decode pieces: first block of the stream, and how many
+    int64_t nblk;
+    int64_t seq_base;    // first u32 of the piece's own token-position area, or -1:
+                         // the shared area indexed by stream offset (as a whole decode)
+    const uint8_t* src;  // edge: first byte of the clip in the staging block
+    uint8_t* dst;        // edge / tail span: where the bytes go
+    int64_t lo;          // tail span: first byte inside the verbatim tail
+    int64_t n;           // edge / tail span: bytes to copy
+    int32_t kind;
+    int32_t pad_;
+};
+// The stream as the range kernels see it.
+struct RangeStream {
+    const uint8_t* in;
+    int64_t in_nbytes;
+    const uint64_t* offs;  // block index (supplied, or rebuilt)
+    int64_t nb;            // blocks of the whole stream
+    int64_t tail;          // verbatim tail bytes of the whole stream
+    uint32_t maxlen;       // largest record payload
+};
+// Decode pieces [0, nd), none of more than max_blk blocks: pieces [0, na) are
+// the first launch's (their work blocks start at 0), [na, nd) the second's (at
+// nblk_a).  Fills wl[] with each
+// work block's header offset (all ones: not inside its piece), and sets every
+// Seg's in_nbytes to the end of its piece's last record and seq0 to its
+// token-position area.
+hipError_t launch_range_worklist(const RangeStream& st, Seg* segs, const RangePiece* pcs, int nd, int na,
+                                 int64_t nblk_a, int64_t max_blk, uint64_t* wl, hipStream_t s);
+// Pieces [0, np): clips of edge blocks whose decode succeeded (res[p] >= 0)
+// and tail spans (res[p] = bytes copied, or -91 when the tail is not inside
+// the stream) to their destinations.
+hipError_t launch_range_edges(const RangeStream& st, const RangePiece* pcs, int64_t* res, int np,
+                              hipStream_t s);
+// *result = -91 when *idx_err (nullptr: an index was supplied) is set, else
+// the code of the last failing piece, else total.
+hipError_t launch_range_reduce(const int64_t* res, int np, const int64_t* idx_err, int64_t total,
+                               int64_t* result, hipStream_t s);
+
 // ---- the reference's internal transpose steps (internals.hip) -------------
 // out[(j * lda + i) * es + t] = in[(i * ldb + j) * es + t]  (bshuf_trans_elem)
 hipError_t launch_trans_elem(const uint8_t* in, uint8_t* out, int64_t lda, int64_t ldb, int64_t es,

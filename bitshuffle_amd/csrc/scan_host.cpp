@@ -1,12 +1,13 @@
 // Host build of the decoder's scan state machine (lz4_scan.h), of the
-// ticket-stealing arithmetic (ticket_steal.h) and of the pipelined encode's
-// segment bounds (pipe_segments.h) for the CPU test suite.  Not part of the
-// product library.
+// ticket-stealing arithmetic (ticket_steal.h), of the pipelined encode's
+// segment bounds (pipe_segments.h) and of the range decode's piece plan
+// (range_plan.h) for the CPU test suite.  Not part of the product library.
 #include <stdint.h>
 
 #include "inplace.h"
 #include "lz4_scan.h"
 #include "pipe_segments.h"
+#include "range_plan.h"
 #include "ticket_steal.h"
 
 namespace {
@@ -79,4 +80,23 @@ extern "C" int bshuf_hostcheck_ticket_victim(const uint32_t* remaining, int own)
     uint32_t r[bshuf::kTicketShards];
     for (int c = 0; c < bshuf::kTicketShards; c++) r[c] = remaining[c];
     return bshuf::ticket_victim(r, own);
+}
+
+// range_plan.h as the range decode uses it.  out[14]: interior b0, b1, dst;
+// head edge blk, lo, hi, dst; tail edge blk, lo, hi, dst; tail span lo, n, dst
+// (dst: byte offsets of the dense output, the range's own being dst0).
+extern "C" void bshuf_hostcheck_range_pieces(int64_t size, int64_t bs, int64_t E, int64_t start,
+                                             int64_t count, int64_t dst0, int64_t* out) {
+    bshuf::RangePieces r;
+    bshuf::range_pieces(size, bs, E, start, count, dst0, r);
+    const int64_t v[14] = {r.b0,      r.b1,      r.int_dst, r.head.blk, r.head.lo, r.head.hi, r.head.dst,
+                           r.tail.blk, r.tail.lo, r.tail.hi, r.tail.dst, r.tail_lo, r.tail_n,  r.tail_dst};
+    for (int i = 0; i < 14; i++) out[i] = v[i];
+}
+// ... for n ranges at once (out: 14 words each)
+extern "C" void bshuf_hostcheck_range_pieces_n(int64_t size, int64_t bs, int64_t E, const int64_t* starts,
+                                               const int64_t* counts, const int64_t* dst0, int64_t n,
+                                               int64_t* out) {
+    for (int64_t i = 0; i < n; i++)
+        bshuf_hostcheck_range_pieces(size, bs, E, starts[i], counts[i], dst0[i], out + 14 * i);
 }

@@ -90,6 +90,40 @@ int64_t bshuf_lz4_block_index_dev(const void* in, size_t in_nbytes, size_t size,
                                   size_t block_size, void* ws, size_t ws_bytes,
                                   uint64_t* block_offsets, int64_t* d_status, void* stream);
 
+/* ---- random-access decode: element ranges of one stream (additive) ----
+ *
+ * Decodes `nranges` element ranges of ONE framed stream into one dense output,
+ * on the device: only the blocks a range touches are decoded.  size, elem_size
+ * and block_size describe the WHOLE array the stream encodes, as for
+ * bshuf_decompress_lz4_dev.  starts[] and counts[] are HOST arrays (read before
+ * the call returns): range i is elements [starts[i], starts[i] + counts[i]).
+ * `out` (device, any byte alignment) receives the ranges' bytes back to back in
+ * list order -- range i begins at byte elem_size * (counts[0] + ... +
+ * counts[i-1]) -- and nothing outside its first elem_size * sum(counts) bytes
+ * is written.  Ranges may overlap, repeat, come in any order and be empty.
+ *
+ * block_offsets: the stream's block index (device; what bshuf_compress_lz4_dev
+ * or bshuf_lz4_block_index_dev wrote), or NULL.  With an index, only the
+ * records of the touched blocks are read (and the last block's header and the
+ * verbatim tail when a range reaches the tail), so a corrupt block cannot
+ * affect a range that does not touch it.  With NULL the index is rebuilt from
+ * the whole stream first; a stream whose records do not tile it gives -91.
+ *
+ * *d_result (device): elem_size * sum(counts) on success, else the negative
+ * code the whole decode reports for a failing block among those decoded here.
+ * Returns 0 once the work is enqueued; nothing synchronises the host.  Host
+ * errors: an invalid block_size as the other entries (-81), a range that does
+ * not lie inside [0, size] or a workspace that is too small or not 256-byte
+ * aligned -71.  The workspace is bshuf_decompress_lz4_ranges_dev_workspace(...)
+ * bytes for the same arguments, or NULL (library pool). */
+size_t bshuf_decompress_lz4_ranges_dev_workspace(size_t in_nbytes, size_t size, size_t elem_size,
+                                                 size_t block_size, const size_t* starts,
+                                                 const size_t* counts, size_t nranges);
+int64_t bshuf_decompress_lz4_ranges_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                        size_t block_size, const size_t* starts, const size_t* counts,
+                                        size_t nranges, void* out, void* ws, size_t ws_bytes,
+                                        int64_t* d_result, const uint64_t* block_offsets, void* stream);
+
 /* ---- batched device entry points (additive) ----
  *
  * `count` independent framed streams per call, all with the same elem_size and
