@@ -22,6 +22,10 @@ the blocks they touch
         one per (start, count) of `ranges`, views of one dense output
     decompress_lz4_range_dev(buf, size, dtype, start, count, ...) -> tensor
     decompress_lz4_ranges_workspace(in_nbytes, size, elem_size, ranges, ...)
+Window decode (device): K windows of one length whose starts are a DEVICE
+tensor the host never reads (replayable under graph capture)
+    decompress_lz4_windows_dev(buf, size, dtype, starts, window, ...) -> (K, window)
+    decompress_lz4_windows_workspace(in_nbytes, size, elem_size, nwindows, window, ...)
 """
 from ._lib import (  # noqa: F401
     LIB_PATH,
@@ -49,6 +53,8 @@ from .api import (  # noqa: F401
     decompress_lz4_range_dev,
     decompress_lz4_ranges_dev,
     decompress_lz4_ranges_workspace,
+    decompress_lz4_windows_dev,
+    decompress_lz4_windows_workspace,
     default_block_size,
     synth_fill_dev,
 )
@@ -76,5 +82,7 @@ __all__ = [
     "decompress_lz4_ranges_dev",
     "decompress_lz4_range_dev",
     "decompress_lz4_ranges_workspace",
+    "decompress_lz4_windows_dev",
+    "decompress_lz4_windows_workspace",
     "FAST_PARSE_VERSION",
 ]

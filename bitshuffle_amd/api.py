@@ -329,6 +329,68 @@ def decompress_lz4_range_dev(buf, size, dtype, start, count, **kw):
     return r if kw.get("sync", True) is False else r[0]
 
 
+def decompress_lz4_windows_workspace(in_nbytes, size, elem_size, nwindows, window, block_size=0,
+                                     device=None):
+    """A workspace for decompress_lz4_windows_dev of `nwindows` windows of
+    `window` elements of a stream of `in_nbytes` bytes: its size depends on
+    these numbers only, never on the starts."""
+    torch = _torch()
+    n = int(lib.bshuf_decompress_lz4_windows_dev_workspace(in_nbytes, size, elem_size, block_size,
+                                                           nwindows, window))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device or "cuda")
+
+
+def decompress_lz4_windows_dev(buf, size, dtype, starts, window, block_size=0, out=None,
+                               workspace=None, result=None, status=None, offsets=None, stream=None,
+                               sync=True, elem_size=None):
+    """Window decode (bshuf_decompress_lz4_windows_dev): K = starts.numel()
+    windows of `window` elements each of the framed stream in uint8 device
+    tensor `buf`, which encodes `size` elements of `dtype`.  `starts` is a
+    contiguous int64 DEVICE tensor of element indices, read by the kernels only:
+    nothing here copies it to the host, and a call captured into a graph decodes
+    whatever starts the tensor holds at each replay.  Returns a (K, window)
+    tensor of `dtype` -- with `elem_size` a uint8 tensor (K, window * elem_size)
+    -- (sync=True), or (out, result) with result a 1-element int64 device tensor
+    of the byte count / error code (sync=False).  `status` (int64 device tensor,
+    K entries): per window its byte count, -71 for a start outside [0, size -
+    window] (that window's part of `out` is left as it was), or the code of a
+    failing block it touches.  `offsets`: the stream's block index; without it
+    the index is rebuilt from the whole stream."""
+    torch = _torch()
+    if not (isinstance(starts, torch.Tensor) and starts.is_cuda and starts.dtype == torch.int64
+            and starts.is_contiguous() and starts.device == buf.device):
+        raise ValueError("starts must be a contiguous int64 tensor on the stream's device")
+    K, window = starts.numel(), int(window)
+    if window < 0:
+        raise ValueError("window must be >= 0, not %d" % window)
+    if out is None:
+        if elem_size is None:
+            out = torch.empty((K, window), dtype=dtype, device=buf.device)
+        else:
+            out = torch.empty((K, window * int(elem_size)), dtype=torch.uint8, device=buf.device)
+    es = out.element_size() if elem_size is None else int(elem_size)
+    if out.numel() * out.element_size() < K * window * es:
+        raise ValueError("out holds %d bytes, the windows need %d"
+                         % (out.numel() * out.element_size(), K * window * es))
+    if status is not None and (status.dtype != torch.int64 or status.numel() < K):
+        raise ValueError("status must be an int64 tensor of %d entries" % K)
+    if result is None:
+        result = torch.empty(1, dtype=torch.int64, device=buf.device)
+    ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+    wsb = workspace.numel() if workspace is not None else 0
+    offp = _dptr(offsets) if offsets is not None else None
+    stp = _dptr(status) if status is not None else None
+    _check(lib.bshuf_decompress_lz4_windows_dev(_dptr(buf), buf.numel(), int(size), es, block_size,
+                                                _dptr(starts), K, window, _dptr(out), ws, wsb,
+                                                _dptr(result), stp, offp, _stream(stream)))
+    if not sync:
+        return out, result
+    count = int(result.item())
+    if count < 0:
+        _fail(count)
+    return out
+
+
 def block_index_dev(buf, size, elem_size, block_size=0, workspace=None, stream=None):
     """The block index of the framed stream in uint8 device tensor `buf` for
     `size` elements of `elem_size` bytes (bshuf_lz4_block_index_dev, the

@@ -17,6 +17,7 @@
 #include "launch.h"
 #include "plan.h"
 #include "range_plan.h"
+#include "window_plan.h"
 
 using namespace bshuf;
 
@@ -883,6 +884,173 @@ int64_t bshuf_decompress_lz4_ranges_dev(const void* in, size_t in_nbytes, size_t
     }
     if (launch_range_edges(st, b.pcs, b.res, (int)np, s) != hipSuccess ||
         launch_range_reduce(b.res, (int)np, idx_err, rp.total, d_result, s) != hipSuccess)
+        return kErrHip;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// fixed-length windows of one stream at device-held starts
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// What the host knows of a window call: everything but the starts.
+struct WindowShape {
+    int64_t K = 0, window = 0;
+    int64_t Mw = 0;         // work blocks per window
+    int64_t seq_words = 0;  // token positions: a private area per window, or (shared_seq) the
+    bool shared_seq = false;  // whole decode's area indexed by stream offset, when that is smaller
+    int64_t pw = 0;         // words of one private area
+    int64_t slot = 0;       // bytes of one staging area
+};
+
+int64_t window_shape(const Plan& p, size_t size, size_t in_nbytes, size_t nwindows, size_t window,
+                     WindowShape& w) {
+    const Layout& L = p.L;
+    if (window > size) return kErrUnsupported;
+    const uint64_t M = window ? ((uint64_t)window + L.bs - 2) / L.bs + 1 : 1;
+    if (nwindows >= ((uint64_t)1 << 31) || M >= ((uint64_t)1 << 31) || nwindows * M >= ((uint64_t)1 << 31))
+        return kErrUnsupported;
+    // (the large-block route decodes one host-known piece at a time)
+    if ((int64_t)L.bs * L.E > max_lds_decode_bytes()) return kErrUnsupported;
+    w.K = (int64_t)nwindows;
+    w.window = (int64_t)window;
+    w.Mw = window ? window_blocks((int64_t)size, L.bs, (int64_t)window) : 0;
+    const int64_t maxlen = lz4_bound(L.bs * L.E);
+    w.pw = w.Mw * (4 + maxlen) / 3 + 80;
+    const int64_t shared_words = (int64_t)in_nbytes / 3 + 80;
+    w.shared_seq = shared_words < w.K * w.pw;
+    w.seq_words = w.shared_seq ? shared_words : w.K * w.pw;
+    w.slot = (w.Mw * (int64_t)L.bs * L.E + 15) & ~(int64_t)15;
+    return 0;
+}
+
+struct WindowBufs {
+    Seg* segs;
+    RangePiece* pcs;
+    WindowTail* wt;
+    uint32_t* blk_seg;
+    DecodeBufs d;    // offs: the work list; idx_err: zeros, one per window
+    int64_t* res;    // one per window: its Seg's result
+    int64_t* wstat;  // one per window, when the caller passes no d_status
+    uint8_t* slots;  // staging areas
+    DecodeBufs idx;  // index rebuild of the whole stream (offs: its block index)
+};
+
+// K Seg, RangePiece and WindowTail records, K * Mw work blocks (map, offsets,
+// status), the token positions, K * Mw staging blocks, and the index rebuild's
+// buffers (carved whether or not the caller supplies an index).
+size_t window_ws(const Plan& p, const WindowShape& w, int64_t blocks_end, WindowBufs* b, uint8_t* base) {
+    Carver c{base};
+    WindowBufs x{};
+    const size_t K = (size_t)w.K, nwork = (size_t)(w.K * w.Mw);
+    x.segs = c.take<Seg>(K * sizeof(Seg));
+    x.pcs = c.take<RangePiece>(K * sizeof(RangePiece));
+    x.wt = c.take<WindowTail>(K * sizeof(WindowTail));
+    x.blk_seg = c.take<uint32_t>(nwork * 4 + 4);
+    x.d.offs = c.take<uint64_t>(nwork * 8 + 8);
+    x.d.status = c.take<int64_t>(nwork * 8 + 8);
+    x.d.seq = c.take<uint32_t>((size_t)w.seq_words * 4);
+    x.d.idx_err = c.take<int64_t>(K * 8 + 8);
+    x.d.bad = c.take<long long>(K * 8 + 8);
+    x.d.tickets = c.take<uint32_t>(kTicketSetBytes);
+    x.res = c.take<int64_t>(K * 8 + 8);
+    x.wstat = c.take<int64_t>(K * 8 + 8);
+    x.slots = c.take<uint8_t>(K * (size_t)w.slot);
+    {
+        x.idx.chunk = index_chunk_bytes(p.L);
+        x.idx.nchunks = blocks_end > 0 ? (blocks_end + x.idx.chunk - 1) / x.idx.chunk : 0;
+        x.idx.offs = c.take<uint64_t>((size_t)p.nb * 8 + 8);
+        x.idx.exits = c.take<int64_t>((size_t)x.idx.nchunks * 8 + 8);
+        x.idx.cnt = c.take<uint64_t>((size_t)(x.idx.nchunks + 1) * 8);
+        x.idx.base = c.take<uint64_t>((size_t)(x.idx.nchunks + 1) * 8);
+        x.idx.idx_err = c.take<int64_t>(8);
+        x.idx.scan_tmp_bytes = decode_scan_tmp_bytes(x.idx.nchunks);
+        x.idx.scan_tmp = c.take<void>(x.idx.scan_tmp_bytes + 8);
+    }
+    if (b) *b = x;
+    return c.off;
+}
+
+}  // namespace
+
+size_t bshuf_decompress_lz4_windows_dev_workspace(size_t in_nbytes, size_t size, size_t elem_size,
+                                                  size_t block_size, size_t nwindows, size_t window) {
+    Plan p;
+    WindowShape w;
+    if (make_plan(size, elem_size, block_size, p) || window_shape(p, size, in_nbytes, nwindows, window, w))
+        return 0;
+    const int64_t cb = (int64_t)in_nbytes - p.tail;
+    return window_ws(p, w, cb > 0 ? cb : 0, nullptr, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                         size_t block_size, const int64_t* d_starts, size_t nwindows,
+                                         size_t window, void* out, void* ws, size_t ws_bytes,
+                                         int64_t* d_result, int64_t* d_status,
+                                         const uint64_t* block_offsets, void* stream) {
+    Plan p;
+    int64_t r = make_plan(size, elem_size, block_size, p);
+    if (r) return r;
+    WindowShape w;
+    r = window_shape(p, size, in_nbytes, nwindows, window, w);
+    if (r) return r;
+    int64_t cb = (int64_t)in_nbytes - p.tail;
+    if (cb < 0) cb = 0;
+    const size_t need = window_ws(p, w, cb, nullptr, nullptr);
+    if (ws && (ws_bytes < need || ((uintptr_t)ws & 255))) return kErrUnsupported;
+    if (!have_device()) return kErrHip;
+    hipStream_t s = (hipStream_t)stream;
+    if (nwindows == 0 || window == 0) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
+    DevBuf own;
+    r = get_ws(ws, ws_bytes, need, own, s);
+    if (r) return r;
+    WindowBufs b;
+    window_ws(p, w, cb, &b, (uint8_t*)ws);
+    const uint8_t* i8 = (const uint8_t*)in;
+    const int K = (int)w.K;
+    int64_t* wstat = d_status ? d_status : b.wstat;
+
+    WindowCall c{};
+    c.in = i8;
+    c.starts = d_starts;
+    c.out = (uint8_t*)out;
+    c.slots = b.slots;
+    c.res = b.res;
+    c.size = (int64_t)size;
+    c.window = w.window;
+    c.wbytes = w.window * p.L.E;
+    c.slot = w.slot;
+    c.Mw = w.Mw;
+    c.seq_words = w.shared_seq ? -1 : w.pw;
+    c.bs = p.L.bs;
+    c.E = p.L.E;
+    c.K = K;
+    if (launch_window_plan(c, b.segs, b.pcs, b.wt, s) != hipSuccess) return kErrHip;
+
+    const uint64_t* offs = block_offsets;
+    const int64_t* idx_err = nullptr;
+    if (!block_offsets) {
+        if (launch_index(i8, cb, p.L, b.idx, s, nullptr, (int64_t)in_nbytes, p.tail) != hipSuccess)
+            return kErrHip;
+        offs = b.idx.offs;
+        idx_err = b.idx.idx_err;
+    }
+    const RangeStream st{i8, (int64_t)in_nbytes, offs, p.nb, p.tail, (uint32_t)lz4_bound(p.L.bs * p.L.E)};
+    if (w.Mw > 0) {
+        // every window's staging area is 16-byte aligned: one scan and one
+        // decode launch over all K * Mw work blocks, no host copy of the table
+        Layout L = p.L;
+        L.nfull = w.K * w.Mw;
+        L.last = 0;
+        if (dev_fill(b.d.idx_err, 0, (size_t)K * 8, s) != hipSuccess ||
+            launch_range_worklist(st, b.segs, b.pcs, K, K, 0, w.Mw, b.d.offs, s) != hipSuccess ||
+            launch_seg_map(b.segs, K, b.blk_seg, false, s) != hipSuccess ||
+            launch_decode_batch(b.segs, nullptr, K, b.blk_seg, L, b.d, s) != hipSuccess)
+            return kErrHip;
+    }
+    if (launch_window_gather(st, c, b.pcs, b.wt, b.d.status, wstat, s) != hipSuccess ||
+        launch_window_reduce(wstat, b.wt, K, idx_err, w.K * c.wbytes, d_result, s) != hipSuccess)
         return kErrHip;
     return 0;
 }

@@ -230,6 +230,9 @@ hipError_t launch_decode_large(const uint8_t* in, int64_t in_nbytes, uint8_t* ou
                                const DecodeBufs& b, uint8_t* shuf, hipStream_t s);
 // Batch versions: L.nfull = total blocks; b.idx_err and b.bad hold one word
 // per stream; chunk_seg / blk_seg map global chunks / blocks to streams.
+// launch_decode_batch reads of hsegs (the host copy of segs) only the alignment
+// of every .out; hsegs == nullptr: the table exists on the device alone, and
+// every .out is 16-byte aligned (the window decode's staging areas).
 hipError_t launch_index_batch(const Seg* segs, int nsegs, const uint32_t* chunk_seg, const Layout& L,
                               int64_t nchunks, const DecodeBufs& b, hipStream_t s);
 hipError_t launch_decode_batch(const Seg* segs, const Seg* hsegs, int nsegs, const uint32_t* blk_seg,
@@ -287,6 +290,48 @@ hipError_t launch_range_edges(const RangeStream& st, const RangePiece* pcs, int6
 // the code of the last failing piece, else total.
 hipError_t launch_range_reduce(const int64_t* res, int np, const int64_t* idx_err, int64_t total,
                                int64_t* result, hipStream_t s);
+
+// ---- window decode (lz4_window.hip) --------------------------------------
+// K windows of the same length at DEVICE-held starts
+// (bshuf_decompress_lz4_windows_dev).  With the length and K known on the host,
+// every table of the range decode has a host-known shape (window_plan.h): window
+// i is one Seg of Mw consecutive blocks, decoded back to back into staging area
+// i, work blocks [i * Mw, (i + 1) * Mw).  k_window_plan writes the tables from
+// the starts; k_range_worklist, launch_seg_map and launch_decode_batch run as
+// in the range decode; k_window_gather copies each window's clip of its staging
+// area and its span of the verbatim tail to the output; k_window_reduce makes
+// the call's result.  No host table depends on the starts.
+struct WindowTail {
+    int64_t lo, n;   // tail span: bytes of the verbatim tail, behind the clip in the window
+    int32_t t0, t1;  // work blocks [t0, t1) of the window hold clip bytes
+    int32_t bad;     // the start was out of range
+    int32_t pad_;
+};
+struct WindowCall {
+    const uint8_t* in;      // the stream
+    const int64_t* starts;  // device, K element indices
+    uint8_t* out;           // window i at out + i * wbytes
+    uint8_t* slots;         // staging areas of `slot` bytes (16-aligned)
+    int64_t* res;           // per window: its Seg's result
+    int64_t size, window;   // elements
+    int64_t wbytes, slot;
+    int64_t Mw;             // work blocks per window
+    int64_t seq_words;      // per window, of its own token-position area; -1: the shared area
+    int32_t bs, E;
+    int32_t K, pad_;
+};
+hipError_t launch_window_plan(const WindowCall& c, Seg* segs, RangePiece* pcs, WindowTail* wt, hipStream_t s);
+// status[i] (wstat): c.wbytes, or -71 (start out of range), the code of the
+// highest failing block that holds clip bytes (dstat: the decode's per-block
+// status; nullptr with res == nullptr: no blocks), or -91 (tail not inside the stream);
+// only windows with c.wbytes are copied.
+hipError_t launch_window_gather(const RangeStream& st, const WindowCall& c, const RangePiece* pcs,
+                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s);
+// *result = -91 when *idx_err (nullptr: an index was supplied) is set, else -71
+// when a start was out of range, else the status of the highest-numbered
+// failing window, else K * wbytes.
+hipError_t launch_window_reduce(const int64_t* wstat, const WindowTail* wt, int K, const int64_t* idx_err,
+                                int64_t total, int64_t* result, hipStream_t s);
 
 // ---- the reference's internal transpose steps (internals.hip) -------------
 // out[(j * lda + i) * es + t] = in[(i * ldb + j) * es + t]  (bshuf_trans_elem)

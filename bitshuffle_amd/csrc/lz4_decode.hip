@@ -2007,7 +2007,7 @@ hipError_t launch_decode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
     if (nb > 0) {
         const int64_t nmax = (int64_t)L.bs * L.E;
         bool aligned = true, al8 = true;
-        for (int i = 0; i < nsegs; i++) {
+        for (int i = 0; hsegs && i < nsegs; i++) {  // (no host copy: every output 16-byte aligned)
             aligned = aligned && ((uintptr_t)hsegs[i].out & 15) == 0;
             al8 = al8 && ((uintptr_t)hsegs[i].out & 7) == 0;
         }

@@ -1,7 +1,8 @@
 // Host build of the decoder's scan state machine (lz4_scan.h), of the
 // ticket-stealing arithmetic (ticket_steal.h), of the pipelined encode's
-// segment bounds (pipe_segments.h) and of the range decode's piece plan
-// (range_plan.h) for the CPU test suite.  Not part of the product library.
+// segment bounds (pipe_segments.h), of the range decode's piece plan
+// (range_plan.h) and of the window decode's plan (window_plan.h) for the CPU
+// test suite.  Not part of the product library.
 #include <stdint.h>
 
 #include "inplace.h"
@@ -9,6 +10,7 @@
 #include "pipe_segments.h"
 #include "range_plan.h"
 #include "ticket_steal.h"
+#include "window_plan.h"
 
 namespace {
 struct HostReader {
@@ -99,4 +101,18 @@ extern "C" void bshuf_hostcheck_range_pieces_n(int64_t size, int64_t bs, int64_t
                                                int64_t* out) {
     for (int64_t i = 0; i < n; i++)
         bshuf_hostcheck_range_pieces(size, bs, E, starts[i], counts[i], dst0[i], out + 14 * i);
+}
+
+// window_plan.h as the window decode uses it, for n (window, start) pairs of
+// one stream.  out, 12 words each: Mw, b0, nfull, last, bad, clip_lo, clip_n,
+// tail_lo, tail_n (bytes), t0, t1, 0.
+extern "C" void bshuf_hostcheck_window_plan(int64_t size, int64_t bs, int64_t E, const int64_t* windows,
+                                            const int64_t* starts, int64_t n, int64_t* out) {
+    for (int64_t i = 0; i < n; i++) {
+        bshuf::WindowPlan w;
+        bshuf::window_plan(size, bs, E, windows[i], starts[i], w);
+        const int64_t v[12] = {bshuf::window_blocks(size, bs, windows[i]), w.b0, w.nfull, w.last, w.bad,
+                               w.clip_lo, w.clip_n, w.tail_lo, w.tail_n, w.t0, w.t1, 0};
+        for (int j = 0; j < 12; j++) out[12 * i + j] = v[j];
+    }
 }

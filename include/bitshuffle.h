@@ -124,6 +124,52 @@ int64_t bshuf_decompress_lz4_ranges_dev(const void* in, size_t in_nbytes, size_t
                                         size_t nranges, void* out, void* ws, size_t ws_bytes,
                                         int64_t* d_result, const uint64_t* block_offsets, void* stream);
 
+/* ---- window decode: fixed-length windows at device-held starts (additive) ----
+ *
+ * Decodes `nwindows` windows of `window` elements each of ONE framed stream.
+ * size, elem_size and block_size describe the WHOLE array, as for the ranges
+ * entry.  d_starts is a DEVICE array of nwindows element indices, read by the
+ * kernels: window i is elements [d_starts[i], d_starts[i] + window), and its
+ * window * elem_size bytes land at out + i * window * elem_size (`out`: device,
+ * any byte alignment; nothing else of it is written).  Windows may overlap,
+ * repeat and come in any order.  The host never sees the starts: the call
+ * never waits on the host, with a caller workspace it allocates nothing, and
+ * captured once into a graph it may be replayed any number of times while the
+ * contents of d_starts change between replays.
+ *
+ * Every window decodes the same number of blocks, Mw = min((window +
+ * block_size - 2) / block_size + 1, blocks of the stream), into a staging area
+ * of its own and is copied from there: the workspace holds nwindows * Mw
+ * staging blocks (block_size * elem_size bytes each) plus per-window and
+ * per-block tables and the token positions --
+ * bshuf_decompress_lz4_windows_dev_workspace(...) bytes, which depend on the
+ * call's shape only, never on the starts -- or NULL (library pool).
+ *
+ * A start that is negative or above size - window is not decoded: that
+ * window's bytes of `out` stay untouched and d_status[i] = -71.  Otherwise
+ * d_status[i] (device, nwindows words, or NULL) is window * elem_size, or the
+ * negative code the whole decode gives for a failing block the window touches
+ * (-91 when the window reaches a verbatim tail that is not inside the stream).
+ * *d_result (device): -91 when the index was rebuilt (block_offsets NULL) and
+ * the records do not tile the stream; else -71 when any start was out of
+ * range; else the status of the highest-numbered failing window; else nwindows
+ * * window * elem_size.  block_offsets as for the ranges entry: with it, only
+ * the records of touched blocks are read (and the last block's header and the
+ * tail bytes when a window reaches the verbatim tail).
+ *
+ * Returns 0 once enqueued (nwindows == 0 or window == 0: *d_result = 0).  Host
+ * errors: an invalid block_size as the other entries (-81); -71 for window >
+ * size, nwindows * ((window + block_size - 2) / block_size + 1) >= 2^31, a block
+ * above the LDS decoder's size (such streams: the ranges entry), a workspace
+ * that is too small or not 256-byte aligned; -70 without a device. */
+size_t bshuf_decompress_lz4_windows_dev_workspace(size_t in_nbytes, size_t size, size_t elem_size,
+                                                  size_t block_size, size_t nwindows, size_t window);
+int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                         size_t block_size, const int64_t* d_starts, size_t nwindows,
+                                         size_t window, void* out, void* ws, size_t ws_bytes,
+                                         int64_t* d_result, int64_t* d_status,
+                                         const uint64_t* block_offsets, void* stream);
+
 /* ---- batched device entry points (additive) ----
  *
  * `count` independent framed streams per call, all with the same elem_size and
