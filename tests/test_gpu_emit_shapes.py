@@ -22,6 +22,8 @@ import numpy as np
 import pytest
 
 from tests import emit_cases as C
+from tests import gpu_run
+from tests.gpu_run import bs, torch, variant  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,41 +32,9 @@ NO_PIPE = 1 << 20
 VARIANTS = [0, OLD_EMIT]
 
 
-@pytest.fixture(scope="module")
-def bs():
-    import bitshuffle_amd
-    assert bitshuffle_amd.using_HIP(), "no HIP device: the GPU suite must run on MI355X"
-    return bitshuffle_amd
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture
-def variant(bs):
-    def set_(v):
-        assert bs.lib.bshuf_set_variant(v) == 0, v
-    yield set_
-    assert bs.lib.bshuf_set_variant(0) == 0
-
-
 def run_case(bs, torch, oracle, variant, blocks, E, block_elems, block_arg=0, tail=b""):
     """Shuffled blocks (+ raw tail bytes) -> input -> device stream == oracle stream."""
-    sh = np.concatenate(list(blocks) + [np.frombuffer(tail, np.uint8)])
-    a = oracle.bitunshuffle(C.view(sh, E), block_elems)
-    want = oracle.compress_lz4(a, block_arg)
-    raw = a.view(np.uint8).reshape(-1)
-    x = torch.from_numpy(raw.copy()).cuda()
-    for v in VARIANTS:
-        variant(v)
-        c = bs.compress_lz4_dev(x, block_arg, elem_size=E)
-        assert c.cpu().numpy().tobytes() == want.tobytes(), v
-    y = bs.decompress_lz4_dev(c, (raw.size // E,), torch.uint8, block_arg, elem_size=E)
-    assert torch.equal(x, y)
+    gpu_run.run_case(bs, torch, oracle, variant, blocks, E, block_elems, block_arg, tail, variants=VARIANTS)
 
 
 @pytest.fixture(scope="module")
