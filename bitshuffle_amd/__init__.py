@@ -26,6 +26,11 @@ Window decode (device): K windows of one length whose starts are a DEVICE
 tensor the host never reads (replayable under graph capture)
     decompress_lz4_windows_dev(buf, size, dtype, starts, window, ...) -> (K, window)
     decompress_lz4_windows_workspace(in_nbytes, size, elem_size, nwindows, window, ...)
+Window decode over a set of streams (device): window i lies in stream ids[i] at
+starts[i], both DEVICE tensors; the set is built once
+    lz4_stream_set_dev(bufs, sizes, elem_size, block_size=0, offsets=None, ...) -> StreamSet
+    decompress_lz4_windows_set_dev(sset, dtype, ids, starts, window, ...) -> (K, window)
+    decompress_lz4_windows_set_workspace(sset, nwindows, window, ...)
 """
 from ._lib import (  # noqa: F401
     LIB_PATH,
@@ -39,6 +44,7 @@ from ._lib import (  # noqa: F401
 )
 from .api import (  # noqa: F401
     FAST_PARSE_VERSION,
+    StreamSet,
     bitshuffle,
     bitshuffle_dev,
     bitunshuffle,
@@ -54,8 +60,11 @@ from .api import (  # noqa: F401
     decompress_lz4_ranges_dev,
     decompress_lz4_ranges_workspace,
     decompress_lz4_windows_dev,
+    decompress_lz4_windows_set_dev,
+    decompress_lz4_windows_set_workspace,
     decompress_lz4_windows_workspace,
     default_block_size,
+    lz4_stream_set_dev,
     synth_fill_dev,
 )
 
@@ -84,5 +93,9 @@ __all__ = [
     "decompress_lz4_ranges_workspace",
     "decompress_lz4_windows_dev",
     "decompress_lz4_windows_workspace",
+    "StreamSet",
+    "lz4_stream_set_dev",
+    "decompress_lz4_windows_set_dev",
+    "decompress_lz4_windows_set_workspace",
     "FAST_PARSE_VERSION",
 ]

@@ -391,6 +391,128 @@ def decompress_lz4_windows_dev(buf, size, dtype, starts, window, block_size=0, o
     return out
 
 
+class StreamSet:
+    """A device-resident table of framed streams that share element and block
+    size (bshuf_lz4_stream_set_dev), for decompress_lz4_windows_set_dev.  The
+    table points into the streams and the supplied block indexes; `bufs` and
+    `offsets` keep them alive.  `status` (int64 device tensor, one entry per
+    stream) is 0, or -91 for a stream whose index was rebuilt here and whose
+    records do not tile it."""
+
+    def __init__(self, table, bufs, offsets, status, sizes, elem_size, block_size):
+        self.table, self.bufs, self.offsets, self.status = table, bufs, offsets, status
+        self.sizes = list(sizes)
+        self.count = len(self.sizes)
+        self.max_size = max(self.sizes) if self.sizes else 0
+        self.elem_size, self.block_size = int(elem_size), int(block_size)
+
+    @property
+    def device(self):
+        return self.table.device
+
+
+def lz4_stream_set_dev(bufs, sizes, elem_size, block_size=0, offsets=None, workspace=None, stream=None):
+    """Build a StreamSet of the framed streams in the uint8 device tensors
+    `bufs`; stream s encodes sizes[s] elements of `elem_size` bytes in blocks of
+    `block_size`.  `offsets`: None, or per stream its block index (what
+    compress_lz4_dev / compress_lz4_batch_dev / block_index_dev wrote) or None;
+    a stream without one gets its index rebuilt here, once.  Enqueues only:
+    read `.status` for the per-stream outcome of the rebuild."""
+    torch = _torch()
+    bufs, sizes = list(bufs), [int(n) for n in sizes]
+    offsets = [None] * len(bufs) if offsets is None else list(offsets)
+    if len(sizes) != len(bufs) or len(offsets) != len(bufs):
+        raise ValueError("bufs, sizes and offsets need one entry per stream")
+    device = bufs[0].device if bufs else (workspace.device if workspace is not None else torch.device("cuda"))
+    for t in bufs + [o for o in offsets if o is not None]:
+        _dptr(t)
+        if t.device != device:
+            raise ValueError("every stream and index of a set lives on one device")
+    es, count = int(elem_size), len(bufs)
+    psz, keep1 = _size_array(sizes)
+    pnb, keep2 = _size_array([b.numel() for b in bufs])
+    pin, keep3 = _ptr_array([b.data_ptr() for b in bufs])
+    poff, keep4 = _ptr_array([o.data_ptr() if o is not None else 0 for o in offsets])
+    nbytes = int(lib.bshuf_lz4_stream_set_dev_bytes(psz, count, es, block_size))
+    if nbytes == 0:
+        # the build's own refusal, before the device is touched
+        _check(lib.bshuf_lz4_stream_set_dev(pin, pnb, psz, count, es, block_size, poff, None, 0, None, 0,
+                                            None, _stream(stream)))
+        _fail(-71)
+    table = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    status = torch.zeros(max(count, 1), dtype=torch.int64, device=device)[:count]
+    ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+    wsb = workspace.numel() if workspace is not None else 0
+    _check(lib.bshuf_lz4_stream_set_dev(pin, pnb, psz, count, es, block_size, poff, _dptr(table), nbytes,
+                                        ws, wsb, ctypes.c_void_p(status.data_ptr()), _stream(stream)))
+    return StreamSet(table, bufs, offsets, status, sizes, es, block_size)
+
+
+def decompress_lz4_windows_set_workspace(sset, nwindows, window, device=None):
+    """A workspace for decompress_lz4_windows_set_dev of `nwindows` windows of
+    `window` elements over StreamSet `sset`: its size depends on the set's
+    largest stream, element and block size and these two numbers only."""
+    torch = _torch()
+    n = int(lib.bshuf_decompress_lz4_windows_set_dev_workspace(sset.max_size, sset.elem_size,
+                                                               sset.block_size, nwindows, window))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device or sset.device)
+
+
+def decompress_lz4_windows_set_dev(sset, dtype, ids, starts, window, out=None, workspace=None, result=None,
+                                   status=None, stream=None, sync=True, elem_size=None):
+    """Window decode over a StreamSet (bshuf_decompress_lz4_windows_set_dev):
+    window i is elements [starts[i], starts[i] + window) of stream ids[i].
+    `ids` and `starts` are contiguous int64 DEVICE tensors of equal length K,
+    read by the kernels only: nothing here copies them to the host, and a call
+    captured into a graph follows both at every replay.  Returns a (K, window)
+    tensor of `dtype` -- with `elem_size` a uint8 tensor (K, window * elem_size)
+    -- (sync=True, which reads only `result`), or (out, result) (sync=False).
+    `status` (int64 device tensor, K entries): per window its byte count; -71
+    for an id outside the set, a start outside [0, size - window] of its stream
+    or a stream of fewer than min((window + block_size - 2) // block_size + 1,
+    blocks of the largest stream) blocks (that window's part of `out` is left as
+    it was); -91 for a stream whose rebuilt index failed; or the code of a
+    failing block the window touches."""
+    torch = _torch()
+    for name, t in (("ids", ids), ("starts", starts)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+                and t.device == sset.device):
+            raise ValueError("%s must be a contiguous int64 tensor on the set's device" % name)
+    if ids.numel() != starts.numel():
+        raise ValueError("ids and starts need one entry per window (%d and %d)" % (ids.numel(), starts.numel()))
+    K, window = starts.numel(), int(window)
+    if window < 0:
+        raise ValueError("window must be >= 0, not %d" % window)
+    if out is None:
+        if elem_size is None:
+            out = torch.empty((K, window), dtype=dtype, device=sset.device)
+        else:
+            out = torch.empty((K, window * int(elem_size)), dtype=torch.uint8, device=sset.device)
+    es = out.element_size() if elem_size is None else int(elem_size)
+    if es != sset.elem_size:
+        raise ValueError("the set holds %d-byte elements, not %d-byte ones" % (sset.elem_size, es))
+    if out.numel() * out.element_size() < K * window * es:
+        raise ValueError("out holds %d bytes, the windows need %d"
+                         % (out.numel() * out.element_size(), K * window * es))
+    if status is not None and (status.dtype != torch.int64 or status.numel() < K):
+        raise ValueError("status must be an int64 tensor of %d entries" % K)
+    if result is None:
+        result = torch.empty(1, dtype=torch.int64, device=sset.device)
+    ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+    wsb = workspace.numel() if workspace is not None else 0
+    stp = _dptr(status) if status is not None else None
+    _check(lib.bshuf_decompress_lz4_windows_set_dev(_dptr(sset.table), sset.count, sset.max_size, es,
+                                                    sset.block_size, _dptr(ids), _dptr(starts), K, window,
+                                                    _dptr(out), ws, wsb, _dptr(result), stp,
+                                                    _stream(stream)))
+    if not sync:
+        return out, result
+    count = int(result.item())
+    if count < 0:
+        _fail(count)
+    return out
+
+
 def block_index_dev(buf, size, elem_size, block_size=0, workspace=None, stream=None):
     """The block index of the framed stream in uint8 device tensor `buf` for
     `size` elements of `elem_size` bytes (bshuf_lz4_block_index_dev, the

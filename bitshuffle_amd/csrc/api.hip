@@ -1055,6 +1055,301 @@ int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// fixed-length windows over a set of streams, stream indices and starts
+// device-held
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// What the host knows of a stream set: the batch table of its index rebuild
+// (streams whose index the caller supplies: no blocks and no chunks there).
+struct SetPlan {
+    BatchPlan bp;               // segs[s].first: stream s's place in the set's index memory
+    std::vector<int64_t> nb;    // blocks per stream
+    int64_t nb_total = 0, nb_max = 0, ref = -1;
+};
+
+int64_t make_set(const void* const* ins, const size_t* in_nbytes, const size_t* sizes, size_t count,
+                 size_t elem_size, size_t block_size, const uint64_t* const* block_offsets, SetPlan& sp) {
+    Plan p0;
+    int64_t r = make_plan(0, elem_size, block_size, p0);
+    if (r) return r;
+    if ((int64_t)p0.L.bs * p0.L.E > max_lds_decode_bytes()) return kErrUnsupported;
+    if (count > (size_t)INT32_MAX) return kErrUnsupported;
+    BatchPlan& bp = sp.bp;
+    bp.L = p0.L;
+    bp.chunk = index_chunk_bytes(p0.L);
+    bp.segs.resize(count);
+    sp.nb.resize(count);
+    for (size_t i = 0; i < count; i++) {
+        Plan p;
+        r = make_plan(sizes[i], elem_size, block_size, p);
+        if (r) return r;
+        const bool own = !(block_offsets && block_offsets[i]);
+        Seg& g = bp.segs[i];
+        g = Seg{};
+        g.in = ins ? (const uint8_t*)ins[i] : nullptr;
+        g.first = sp.nb_total;
+        g.nfull = own ? p.L.nfull : 0;
+        g.last = own ? p.L.last : 0;
+        g.tail = p.tail;
+        g.in_nbytes = in_nbytes ? (int64_t)in_nbytes[i] : 0;
+        const int64_t cb = std::max<int64_t>(g.in_nbytes - g.tail, 0);
+        g.chunk0 = bp.nchunks;
+        g.nchunks = own && cb > 0 ? (cb + bp.chunk - 1) / bp.chunk : 0;
+        bp.nchunks += g.nchunks;
+        sp.nb[i] = p.nb;
+        sp.nb_total += p.nb;
+        if (sp.ref < 0 || p.nb > sp.nb_max) {
+            sp.nb_max = p.nb;
+            sp.ref = (int64_t)i;
+        }
+        if (sp.nb_total >= ((int64_t)1 << 31) || bp.nchunks >= ((int64_t)1 << 31)) return kErrUnsupported;
+    }
+    bp.nb = sp.nb_total;
+    bp.L.nfull = sp.nb_total;
+    bp.L.last = 0;
+    return 0;
+}
+
+size_t set_bytes_of(size_t count, int64_t nb_total) {
+    return al256(kStreamSetRecs + count * sizeof(StreamSetRec)) + al256((size_t)nb_total * 8 + 8);
+}
+
+struct SetBufs {
+    Seg* segs;
+    uint32_t* chunk_seg;
+    DecodeBufs idx;
+};
+
+// the batched index rebuild's buffers, sized as if no index were supplied
+size_t set_ws(const SetPlan& sp, SetBufs* b, uint8_t* base) {
+    Carver c{base};
+    SetBufs x{};
+    const size_t ns = sp.bp.segs.size(), nch = (size_t)sp.bp.nchunks;
+    x.segs = c.take<Seg>(ns * sizeof(Seg) + 8);
+    x.chunk_seg = c.take<uint32_t>(nch * 4 + 4);
+    x.idx.chunk = sp.bp.chunk;
+    x.idx.nchunks = sp.bp.nchunks;
+    x.idx.exits = c.take<int64_t>(nch * 8 + 8);
+    x.idx.cnt = c.take<uint64_t>((nch + 1) * 8);
+    x.idx.base = c.take<uint64_t>((nch + 1) * 8);
+    x.idx.idx_err = c.take<int64_t>(ns * 8 + 8);
+    x.idx.scan_tmp_bytes = decode_scan_tmp_bytes(sp.bp.nchunks);
+    x.idx.scan_tmp = c.take<void>(x.idx.scan_tmp_bytes + 8);
+    if (b) *b = x;
+    return c.off;
+}
+
+}  // namespace
+
+size_t bshuf_lz4_stream_set_dev_bytes(const size_t* sizes, size_t count, size_t elem_size, size_t block_size) {
+    SetPlan sp;
+    if (make_set(nullptr, nullptr, sizes, count, elem_size, block_size, nullptr, sp)) return 0;
+    return set_bytes_of(count, sp.nb_total);
+}
+
+size_t bshuf_lz4_stream_set_dev_workspace(const size_t* in_nbytes, const size_t* sizes, size_t count,
+                                          size_t elem_size, size_t block_size) {
+    SetPlan sp;
+    if (make_set(nullptr, in_nbytes, sizes, count, elem_size, block_size, nullptr, sp)) return 0;
+    return set_ws(sp, nullptr, nullptr);
+}
+
+int64_t bshuf_lz4_stream_set_dev(const void* const* ins, const size_t* in_nbytes, const size_t* sizes,
+                                 size_t count, size_t elem_size, size_t block_size,
+                                 const uint64_t* const* block_offsets, void* d_set, size_t set_bytes, void* ws,
+                                 size_t ws_bytes, int64_t* d_status, void* stream) {
+    SetPlan sp, full;
+    int64_t r = make_set(ins, in_nbytes, sizes, count, elem_size, block_size, block_offsets, sp);
+    if (r) return r;
+    // the workspace is sized without a look at which indexes are supplied
+    r = make_set(nullptr, in_nbytes, sizes, count, elem_size, block_size, nullptr, full);
+    if (r) return r;
+    const size_t need = set_ws(full, nullptr, nullptr);
+    if (!d_set || ((uintptr_t)d_set & 255) || set_bytes < set_bytes_of(count, sp.nb_total)) return kErrUnsupported;
+    if (ws && (ws_bytes < need || ((uintptr_t)ws & 255))) return kErrUnsupported;
+    if (!have_device()) return kErrHip;
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf own;
+    r = get_ws(ws, ws_bytes, need, own, s);
+    if (r) return r;
+    SetBufs b;
+    set_ws(sp, &b, (uint8_t*)ws);
+
+    uint8_t* set8 = (uint8_t*)d_set;
+    uint64_t* index = (uint64_t*)(set8 + al256(kStreamSetRecs + count * sizeof(StreamSetRec)));
+    std::vector<uint8_t> table(kStreamSetRecs + count * sizeof(StreamSetRec), 0);
+    StreamSetHeader h{};
+    h.magic = kStreamSetMagic;
+    h.count = (int64_t)count;
+    h.E = sp.bp.L.E;
+    h.bs = sp.bp.L.bs;
+    h.nb_max = sp.nb_max;
+    h.ref = sp.ref;
+    memcpy(table.data(), &h, sizeof(h));
+    const uint32_t maxlen = (uint32_t)lz4_bound(sp.bp.L.bs * sp.bp.L.E);
+    for (size_t i = 0; i < count; i++) {
+        const Seg& g = sp.bp.segs[i];
+        StreamSetRec rec{};
+        rec.st.in = g.in;
+        rec.st.in_nbytes = g.in_nbytes;
+        rec.st.offs = block_offsets && block_offsets[i] ? block_offsets[i] : index + g.first;
+        rec.st.nb = sp.nb[i];
+        rec.st.tail = g.tail;
+        rec.st.maxlen = maxlen;
+        rec.size = (int64_t)sizes[i];
+        memcpy(table.data() + kStreamSetRecs + i * sizeof(StreamSetRec), &rec, sizeof(rec));
+    }
+    if (stage_upload(table.data(), table.size(), d_set, s) != hipSuccess) return kErrHip;
+    if (count == 0) return 0;
+    b.idx.offs = index;
+    if (stage_upload(sp.bp.segs.data(), count * sizeof(Seg), b.segs, s) != hipSuccess ||
+        launch_seg_map(b.segs, (int)count, b.chunk_seg, true, s) != hipSuccess ||
+        launch_index_batch(b.segs, (int)count, b.chunk_seg, sp.bp.L, sp.bp.nchunks, b.idx, s) != hipSuccess ||
+        launch_stream_set_status((StreamSetRec*)(set8 + kStreamSetRecs), b.idx.idx_err, d_status, (int)count,
+                                 s) != hipSuccess)
+        return kErrHip;
+    return 0;
+}
+
+namespace {
+
+// What the host knows of a window call over a set: everything but ids and starts.
+struct WindowSetShape {
+    int64_t K = 0, window = 0;
+    int64_t nb_max = 0;
+    int64_t Mw = 0;    // work blocks per window
+    int64_t pw = 0;    // words of one window's token-position area
+    int64_t slot = 0;  // bytes of one staging area
+};
+
+int64_t window_set_shape(const Plan& p, size_t max_size, size_t nwindows, size_t window, WindowSetShape& w) {
+    const Layout& L = p.L;
+    if (window > max_size) return kErrUnsupported;
+    const uint64_t M = window ? ((uint64_t)window + L.bs - 2) / L.bs + 1 : 1;
+    if (nwindows >= ((uint64_t)1 << 31) || M >= ((uint64_t)1 << 31) || nwindows * M >= ((uint64_t)1 << 31))
+        return kErrUnsupported;
+    if ((int64_t)L.bs * L.E > max_lds_decode_bytes()) return kErrUnsupported;
+    w.K = (int64_t)nwindows;
+    w.window = (int64_t)window;
+    w.nb_max = p.nb;
+    w.Mw = window ? window_blocks((int64_t)max_size, L.bs, (int64_t)window) : 0;
+    w.pw = w.Mw * (4 + (int64_t)lz4_bound(L.bs * L.E)) / 3 + 80;
+    w.slot = (w.Mw * (int64_t)L.bs * L.E + 15) & ~(int64_t)15;
+    return 0;
+}
+
+struct WindowSetBufs {
+    Seg* segs;
+    RangePiece* pcs;
+    WindowTail* wt;
+    int32_t* sidx;   // per window: its stream
+    uint32_t* blk_seg;
+    DecodeBufs d;    // offs: the work list; idx_err: zeros, one per window
+    int64_t* res;    // one per window: its Seg's result
+    int64_t* wstat;  // one per window, when the caller passes no d_status
+    uint8_t* slots;  // staging areas
+};
+
+size_t window_set_ws(const WindowSetShape& w, WindowSetBufs* b, uint8_t* base) {
+    Carver c{base};
+    WindowSetBufs x{};
+    const size_t K = (size_t)w.K, nwork = (size_t)(w.K * w.Mw);
+    x.segs = c.take<Seg>(K * sizeof(Seg));
+    x.pcs = c.take<RangePiece>(K * sizeof(RangePiece));
+    x.wt = c.take<WindowTail>(K * sizeof(WindowTail));
+    x.sidx = c.take<int32_t>(K * 4 + 4);
+    x.blk_seg = c.take<uint32_t>(nwork * 4 + 4);
+    x.d.offs = c.take<uint64_t>(nwork * 8 + 8);
+    x.d.status = c.take<int64_t>(nwork * 8 + 8);
+    x.d.seq = c.take<uint32_t>(K * (size_t)w.pw * 4);
+    x.d.idx_err = c.take<int64_t>(K * 8 + 8);
+    x.d.bad = c.take<long long>(K * 8 + 8);
+    x.d.tickets = c.take<uint32_t>(kTicketSetBytes);
+    x.res = c.take<int64_t>(K * 8 + 8);
+    x.wstat = c.take<int64_t>(K * 8 + 8);
+    x.slots = c.take<uint8_t>(K * (size_t)w.slot);
+    if (b) *b = x;
+    return c.off;
+}
+
+}  // namespace
+
+size_t bshuf_decompress_lz4_windows_set_dev_workspace(size_t max_size, size_t elem_size, size_t block_size,
+                                                      size_t nwindows, size_t window) {
+    Plan p;
+    WindowSetShape w;
+    if (make_plan(max_size, elem_size, block_size, p) || window_set_shape(p, max_size, nwindows, window, w))
+        return 0;
+    return window_set_ws(w, nullptr, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                             size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                             size_t nwindows, size_t window, void* out, void* ws,
+                                             size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                             void* stream) {
+    Plan p;
+    int64_t r = make_plan(max_size, elem_size, block_size, p);
+    if (r) return r;
+    WindowSetShape w;
+    r = window_set_shape(p, max_size, nwindows, window, w);
+    if (r) return r;
+    if (count > (size_t)INT32_MAX) return kErrUnsupported;
+    const size_t need = window_set_ws(w, nullptr, nullptr);
+    if (ws && (ws_bytes < need || ((uintptr_t)ws & 255))) return kErrUnsupported;
+    if (!d_set || ((uintptr_t)d_set & 255)) return kErrUnsupported;
+    if (!have_device()) return kErrHip;
+    hipStream_t s = (hipStream_t)stream;
+    if (nwindows == 0 || window == 0) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
+    DevBuf own;
+    r = get_ws(ws, ws_bytes, need, own, s);
+    if (r) return r;
+    WindowSetBufs b;
+    window_set_ws(w, &b, (uint8_t*)ws);
+    const int K = (int)w.K;
+    int64_t* wstat = d_status ? d_status : b.wstat;
+
+    WindowSetCall c{};
+    c.hdr = (const StreamSetHeader*)d_set;
+    c.recs = (const StreamSetRec*)((const uint8_t*)d_set + kStreamSetRecs);
+    c.ids = d_ids;
+    c.starts = d_starts;
+    c.out = (uint8_t*)out;
+    c.slots = b.slots;
+    c.res = b.res;
+    c.sidx = b.sidx;
+    c.count = (int64_t)count;
+    c.nb_max = w.nb_max;
+    c.window = w.window;
+    c.wbytes = w.window * p.L.E;
+    c.slot = w.slot;
+    c.Mw = w.Mw;
+    c.seq_words = w.pw;
+    c.bs = p.L.bs;
+    c.E = p.L.E;
+    c.K = K;
+    if (launch_window_set_plan(c, b.segs, b.pcs, b.wt, s) != hipSuccess) return kErrHip;
+    if (w.Mw > 0) {
+        // as the window decode of one stream: one scan and one decode launch
+        // over all K * Mw work blocks, no host copy of the table
+        Layout L = p.L;
+        L.nfull = w.K * w.Mw;
+        L.last = 0;
+        if (dev_fill(b.d.idx_err, 0, (size_t)K * 8, s) != hipSuccess ||
+            launch_window_set_worklist(c, b.segs, b.pcs, b.d.offs, s) != hipSuccess ||
+            launch_seg_map(b.segs, K, b.blk_seg, false, s) != hipSuccess ||
+            launch_decode_batch(b.segs, nullptr, K, b.blk_seg, L, b.d, s) != hipSuccess)
+            return kErrHip;
+    }
+    if (launch_window_set_gather(c, b.pcs, b.wt, b.d.status, wstat, s) != hipSuccess ||
+        launch_window_reduce(wstat, b.wt, K, nullptr, w.K * c.wbytes, d_result, s) != hipSuccess)
+        return kErrHip;
+    return 0;
+}
+
 int64_t bshuf_synth_fill_dev(void* out, size_t n_elem, int gen, uint64_t first, uint64_t seed,
                              void* stream) {
     if (gen < 0 || gen > 2) return kErrUnsupported;

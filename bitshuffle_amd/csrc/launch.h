@@ -333,6 +333,64 @@ hipError_t launch_window_gather(const RangeStream& st, const WindowCall& c, cons
 hipError_t launch_window_reduce(const int64_t* wstat, const WindowTail* wt, int K, const int64_t* idx_err,
                                 int64_t total, int64_t* result, hipStream_t s);
 
+// ---- window decode over a set of streams (lz4_window_set.hip) --------------
+// A stream set (bshuf_lz4_stream_set_dev) is a device table of `count` framed
+// streams that share E and bs: a header, one record per stream, and the block
+// indexes the build rebuilt (a stream whose index the caller supplied keeps the
+// caller's pointer).  bshuf_decompress_lz4_windows_set_dev decodes K windows of
+// one length; window i is elements [starts[i], starts[i] + L) of stream ids[i],
+// both DEVICE arrays.  The shape is the window decode's with Mw = min(M, blocks
+// of the set's largest stream) for every window, and a token-position area per
+// window (offsets of different streams collide in a shared one).  A bad window
+// (window_plan.h, window_set_plan) decodes blocks [0, Mw) of stream `ref`, which
+// has that many, so the work list stays dense and inside a real stream; nothing
+// of that decode is used.  When the header does not match the call, every
+// window is bad and there is no stream to trust: their work blocks then hold
+// the sentinel offset, which the decoder rejects without reading anything.
+constexpr uint64_t kStreamSetMagic = 0x3154455346485342ull;  // "BSHFSET1"
+struct StreamSetHeader {
+    uint64_t magic;
+    int64_t count, E, bs;
+    int64_t nb_max;  // blocks of the largest stream
+    int64_t ref;     // a stream with nb_max blocks (-1: count == 0)
+    int64_t pad_[2];
+};
+struct StreamSetRec {
+    RangeStream st;
+    int64_t size;  // elements
+    int64_t err;   // 0, or -91: the index was rebuilt and the records do not tile the stream
+};
+constexpr size_t kStreamSetRecs = 256;  // byte offset of the records in a set
+static_assert(sizeof(StreamSetHeader) == 64 && sizeof(StreamSetRec) == 64, "stream set layout");
+// rec[s].err and status[s] from the index rebuild's error words (0 -> 0, else -91)
+hipError_t launch_stream_set_status(StreamSetRec* recs, const int64_t* idx_err, int64_t* status, int count,
+                                    hipStream_t s);
+struct WindowSetCall {
+    const StreamSetHeader* hdr;
+    const StreamSetRec* recs;
+    const int64_t* ids;     // device, K stream indices
+    const int64_t* starts;  // device, K element indices
+    uint8_t* out;           // window i at out + i * wbytes
+    uint8_t* slots;         // staging areas of `slot` bytes (16-aligned)
+    int64_t* res;           // per window: its Seg's result
+    int32_t* sidx;          // per window: the stream its blocks come from (-1: none, sentinel offsets)
+    int64_t count, nb_max;  // what the call says of the set
+    int64_t window, wbytes, slot;
+    int64_t Mw;             // work blocks per window
+    int64_t seq_words;      // per window, of its own token-position area
+    int32_t bs, E;
+    int32_t K, pad_;
+};
+hipError_t launch_window_set_plan(const WindowSetCall& c, Seg* segs, RangePiece* pcs, WindowTail* wt,
+                                  hipStream_t s);
+// k_range_worklist with every piece's stream taken from the set's record of c.sidx[piece]
+hipError_t launch_window_set_worklist(const WindowSetCall& c, Seg* segs, const RangePiece* pcs, uint64_t* wl,
+                                      hipStream_t s);
+// launch_window_gather with a stream per window: the tail is found through that
+// stream's last header, and the stream's error word (-91) is the window's status
+hipError_t launch_window_set_gather(const WindowSetCall& c, const RangePiece* pcs, const WindowTail* wt,
+                                    const int64_t* dstat, int64_t* wstat, hipStream_t s);
+
 // ---- the reference's internal transpose steps (internals.hip) -------------
 // out[(j * lda + i) * es + t] = in[(i * ldb + j) * es + t]  (bshuf_trans_elem)
 hipError_t launch_trans_elem(const uint8_t* in, uint8_t* out, int64_t lda, int64_t ldb, int64_t es,

@@ -6,16 +6,12 @@
 // the batch decoder's, unchanged; k_window_gather copies every window out of
 // its staging area and the verbatim tail, k_window_reduce makes the result.
 #include "launch.h"
+#include "window_copy.h"
 #include "window_plan.h"
 
 namespace bshuf {
 
 namespace {
-
-__device__ __forceinline__ uint32_t be32_at(const uint8_t* p) {
-    const gbl8c* q = (const gbl8c*)p;
-    return ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
-}
 
 // One thread per window: its Seg (Mw consecutive blocks of the stream, decoded
 // back to back into staging area i), its piece (the clip of that area) and its
@@ -63,54 +59,6 @@ __global__ __launch_bounds__(256) void k_window_plan(WindowCall c, Seg* __restri
     wt[i] = t;
 }
 
-// 16 bytes of dst from two aligned 16-byte granules of a source that lies
-// 4 * D + sh bytes behind an aligned address.
-template <int D>
-__device__ __forceinline__ u32x4 shifted(const u32x4 a, const u32x4 b, uint32_t sh) {
-    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return u32x4{__builtin_amdgcn_alignbyte(w[D + 1], w[D], sh), __builtin_amdgcn_alignbyte(w[D + 2], w[D + 1], sh),
-                 __builtin_amdgcn_alignbyte(w[D + 3], w[D + 2], sh), __builtin_amdgcn_alignbyte(w[D + 4], w[D + 3], sh)};
-}
-
-template <int D>
-__device__ __forceinline__ void copy_shifted(const gbl128c* q, gbl128* d16, int64_t nv, uint32_t sh, int t,
-                                             int T) {
-    for (int64_t i = t; i < nv; i += T) d16[i] = shifted<D>(q[i], q[i + 1], sh);
-}
-
-// n bytes src -> dst by lanes t of T.  dst is written in whole 16-byte chunks
-// between its first and last 16-byte boundary (the bytes before and behind
-// singly), and nothing outside [0, n) of it.  The source: 16-byte loads when it
-// is congruent to dst mod 16; else every chunk from the two aligned granules
-// that hold its bytes -- a granule holds at least one byte of [0, n), so a read
-// never leaves the pages of the source.  Fewer than 32 bytes go singly.
-__device__ __forceinline__ void span_copy(const uint8_t* src, uint8_t* dst, int64_t n, int t, int T) {
-    const gbl8c* s8 = (const gbl8c*)src;
-    gbl8* d8 = (gbl8*)dst;
-    if (n < 32) {
-        for (int64_t i = t; i < n; i += T) d8[i] = s8[i];
-        return;
-    }
-    const int64_t head = (int64_t)((16 - ((uintptr_t)dst & 15)) & 15);
-    const int64_t nv = (n - head) >> 4;
-    if (t < head) d8[t] = s8[t];
-    gbl128* d16 = (gbl128*)(dst + head);
-    const uint32_t r = (uint32_t)((uintptr_t)(src + head) & 15);
-    if (r == 0) {
-        const gbl128c* s16 = (const gbl128c*)(src + head);
-        for (int64_t i = t; i < nv; i += T) d16[i] = s16[i];
-    } else {
-        const gbl128c* q = g128_aligned_down(src + head);
-        switch (r >> 2) {
-            case 0: copy_shifted<0>(q, d16, nv, r & 3, t, T); break;
-            case 1: copy_shifted<1>(q, d16, nv, r & 3, t, T); break;
-            case 2: copy_shifted<2>(q, d16, nv, r & 3, t, T); break;
-            default: copy_shifted<3>(q, d16, nv, r & 3, t, T); break;
-        }
-    }
-    for (int64_t i = head + 16 * nv + t; i < n; i += T) d8[i] = s8[i];
-}
-
 // T lanes per window, 256 / T windows per workgroup.  The window's status:
 // -71 for a start out of range; else the code of the highest failing block
 // among those that hold clip bytes (the Seg's result says whether any of its Mw
@@ -127,37 +75,8 @@ __global__ __launch_bounds__(256) void k_window_gather(RangeStream st, WindowCal
     const int t = (int)(threadIdx.x % T);
     if (i >= c.K) return;
     const WindowTail w = wt[i];
-    int64_t code = 0;
-    const uint8_t* tsrc = nullptr;
-    if (w.bad) {
-        code = -71;
-    } else {
-        if (w.t1 > w.t0 && c.res[i] < 0) {
-            const int64_t* bst = dstat + (int64_t)i * c.Mw;
-            for (int j = w.t0; j < w.t1; j++)
-                if (bst[j] < 0) code = bst[j];
-        }
-        if (code == 0 && w.n > 0) {
-            const uint64_t N = (uint64_t)st.in_nbytes;
-            uint64_t ts = 0;
-            bool ok = true;
-            if (st.nb > 0) {
-                const uint64_t h = st.offs[st.nb - 1];
-                ok = h <= N && N - h >= 4;
-                if (ok) ts = h + 4 + be32_at(st.in + h);
-            }
-            ok = ok && ts <= N && N - ts >= (uint64_t)st.tail;
-            if (ok)
-                tsrc = st.in + ts + w.lo;
-            else
-                code = -91;
-        }
-    }
-    if (t == 0) wstat[i] = code ? code : c.wbytes;
-    if (code) return;
-    const RangePiece pc = pcs[i];
-    if (pc.n > 0) span_copy(pc.src, pc.dst, pc.n, t, T);
-    if (w.n > 0) span_copy(tsrc, pc.dst + pc.n, w.n, t, T);
+    window_gather_one(st, 0, w, pcs, i, w.t1 > w.t0 ? c.res[i] : 0, dstat + (int64_t)i * c.Mw, c.wbytes, wstat,
+                      t, T);
 }
 
 __global__ __launch_bounds__(256) void k_window_reduce(const int64_t* __restrict__ wstat,

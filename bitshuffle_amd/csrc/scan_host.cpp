@@ -116,3 +116,19 @@ extern "C" void bshuf_hostcheck_window_plan(int64_t size, int64_t bs, int64_t E,
         for (int j = 0; j < 12; j++) out[12 * i + j] = v[j];
     }
 }
+
+// ... and the plan of windows over a set of `count` streams of sizes[] as
+// k_window_set_plan runs it: n (id, window, start) triples, every one with Mw
+// forced.  out as above (word 0: Mw as given).
+extern "C" void bshuf_hostcheck_window_set_plan(int64_t count, const int64_t* sizes, int64_t bs, int64_t E,
+                                                int64_t Mw, const int64_t* ids, const int64_t* windows,
+                                                const int64_t* starts, int64_t n, int64_t* out) {
+    for (int64_t i = 0; i < n; i++) {
+        bshuf::WindowPlan w;
+        const int64_t size = ids[i] >= 0 && ids[i] < count ? sizes[ids[i]] : 0;
+        bshuf::window_set_plan(count, ids[i], size, bs, E, windows[i], starts[i], Mw, w);
+        const int64_t v[12] = {Mw, w.b0, w.nfull, w.last, w.bad, w.clip_lo, w.clip_n, w.tail_lo, w.tail_n,
+                               w.t0, w.t1, 0};
+        for (int j = 0; j < 12; j++) out[12 * i + j] = v[j];
+    }
+}

@@ -2,7 +2,8 @@
 // decode sees it (bshuf_decompress_lz4_windows_dev; launch.h, "window decode").
 // One pure function, run per window by k_window_plan on the device (the starts
 // live in device memory) and by the CPU suite through libbshuf_hostcheck.so:
-// no HIP but the qualifiers below.
+// no HIP but the qualifiers below.  window_set_plan, at the end, is the same for
+// a window in one of a set of streams (bshuf_decompress_lz4_windows_set_dev).
 //
 // The stream of `size` elements in blocks of `bs` (plan.h, make_plan): nfull
 // full blocks, one partial block of `last` elements when that is not 0, then
@@ -45,15 +46,16 @@ BSHUF_WINDOW_FN int64_t window_blocks(int64_t size, int64_t bs, int64_t window) 
     return m < nb ? m : nb;
 }
 
-// 1 <= window <= size (checked by the caller); any start.
-BSHUF_WINDOW_FN void window_plan(int64_t size, int64_t bs, int64_t E, int64_t window, int64_t start,
-                                 WindowPlan& w) {
+// The plan of one window that decodes Mw consecutive blocks of its stream
+// (Mw <= nb, and at least the blocks a window of that length can touch); bad:
+// nothing of the window is copied, blocks [0, Mw) are decoded.
+BSHUF_WINDOW_FN void window_plan_blocks(int64_t size, int64_t bs, int64_t E, int64_t window, int64_t start,
+                                        int64_t Mw, bool bad, WindowPlan& w) {
     const int64_t sfull = size / bs;
     const int64_t slast = size % bs - size % 8;
     const int64_t covered = sfull * bs + slast;  // the blocks' elements
     const int64_t nb = sfull + (slast ? 1 : 0);
-    const int64_t Mw = window_blocks(size, bs, window);
-    w.bad = (start < 0 || start > size - window) ? 1 : 0;
+    w.bad = bad ? 1 : 0;
     const int64_t s = w.bad ? 0 : start;
     int64_t b0 = s / bs;
     if (b0 > nb - Mw) b0 = nb - Mw;  // (nb == 0: Mw == 0 and b0 == 0)
@@ -77,6 +79,43 @@ BSHUF_WINDOW_FN void window_plan(int64_t size, int64_t bs, int64_t E, int64_t wi
         w.tail_lo = (from - covered) * E;
         w.tail_n = (end - from) * E;
     }
+}
+
+// 1 <= window <= size (checked by the caller); any start.
+BSHUF_WINDOW_FN void window_plan(int64_t size, int64_t bs, int64_t E, int64_t window, int64_t start,
+                                 WindowPlan& w) {
+    window_plan_blocks(size, bs, E, window, start, window_blocks(size, bs, window),
+                       start < 0 || start > size - window, w);
+}
+
+// ---- windows over a set of streams (bshuf_decompress_lz4_windows_set_dev) ----
+// Window i of such a call is elements [start, start + window) of stream `id` of
+// `count` streams that share bs and E.  Every window of the call decodes the
+// same number of blocks, Mw = min((window + bs - 2) / bs + 1, blocks of the
+// set's largest stream), whatever its stream: one shape per call.  `size` is
+// stream id's element count (anything when id is outside [0, count)).  The
+// window is bad -- status -71, nothing copied -- when id is outside [0, count),
+// window > size, start is outside [0, size - window], or the stream has fewer
+// than Mw blocks.  A good window gets window_plan's result for its stream with
+// Mw forced (a stream of at least Mw blocks holds every block a window of that
+// length touches: Mw is either that bound or all blocks of the largest stream).
+// A bad one has nothing to copy and b0 = 0: with only its start out of range it
+// is window_plan's bad window of its stream, else Mw full blocks; the caller
+// decodes blocks [0, Mw) of a stream that has them in its place.
+BSHUF_WINDOW_FN void window_set_plan(int64_t count, int64_t id, int64_t size, int64_t bs, int64_t E,
+                                     int64_t window, int64_t start, int64_t Mw, WindowPlan& w) {
+    bool bad = id < 0 || id >= count || window > size;
+    if (!bad) {
+        const int64_t nb = size / bs + (size % bs - size % 8 ? 1 : 0);
+        bad = nb < Mw;
+    }
+    if (bad) {
+        w = WindowPlan{};
+        w.nfull = Mw;
+        w.bad = 1;
+        return;
+    }
+    window_plan_blocks(size, bs, E, window, start, Mw, start < 0 || start > size - window, w);
 }
 
 }  // namespace bshuf

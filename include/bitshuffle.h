@@ -170,6 +170,82 @@ int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_
                                          int64_t* d_result, int64_t* d_status,
                                          const uint64_t* block_offsets, void* stream);
 
+/* ---- window decode over a set of streams (additive) ----
+ *
+ * Data is rarely one stream: an HDF5 dataset under filter 32008 is one stream
+ * per chunk, bshuf_compress_lz4_batch_dev makes one per tensor.  A STREAM SET
+ * is a device-resident table of `count` framed streams that share elem_size and
+ * block_size, built once; the window decode over it takes, per window, the
+ * index of its stream and its start, both from DEVICE arrays.
+ *
+ * bshuf_lz4_stream_set_dev builds the set into d_set (device, 256-byte aligned,
+ * bshuf_lz4_stream_set_dev_bytes(...) bytes).  ins[], in_nbytes[], sizes[] and
+ * block_offsets[] are HOST arrays of device pointers / sizes, as for the batch
+ * entries; block_offsets is NULL, or holds per stream that stream's block index
+ * or NULL.  A stream without a supplied index gets its index rebuilt HERE, once,
+ * into the set's own memory; d_status[s] (device, count words) is then 0, or
+ * -91 when that stream's records do not tile it (every window in it will report
+ * -91; the other streams are not affected).  The set holds POINTERS into the
+ * streams and into every supplied index: they must stay alive and unchanged in
+ * place for as long as the set is used (their contents may change between
+ * calls only where the index stays right).  d_set layout: a header (magic
+ * word, count, elem_size, block_size, the largest stream's block count nb_max
+ * and the index of one stream with that many blocks), one 64-byte record per
+ * stream at byte 256 (stream pointer and length, index pointer, block count,
+ * tail bytes, largest record, element count, error word), then the rebuilt
+ * indexes.  The workspace (bshuf_lz4_stream_set_dev_workspace(...) bytes, or
+ * NULL: library pool) is only needed until the build has run.  count == 0 is
+ * valid: a set no window can address.  Host errors: -81 for an invalid
+ * block_size; -71 for a block above the LDS decoder's size, a set_bytes or
+ * ws_bytes that is too small, d_set or ws not 256-byte aligned, 2^31 or more
+ * blocks or index chunks in all; -70 without a device.  The two size functions
+ * return 0 for arguments the build refuses.
+ *
+ * bshuf_decompress_lz4_windows_set_dev decodes nwindows windows of `window`
+ * elements: window i is elements [d_starts[i], d_starts[i] + window) of stream
+ * d_ids[i], and lands at out + i * window * elem_size, as in the single-stream
+ * entry.  count, elem_size and block_size are the set's; max_size is the element
+ * count of its largest stream.  Every window decodes Mw = min((window +
+ * block_size - 2) / block_size + 1, nb_max) consecutive blocks of its stream
+ * into a staging area of its own, so the call's launches and its workspace
+ * (bshuf_decompress_lz4_windows_set_dev_workspace(...) bytes, or NULL) depend on
+ * count, max_size, elem_size, block_size, nwindows and window alone: the host
+ * never reads ids or starts, nothing is uploaded, nothing synchronises, and a
+ * call captured into a graph follows both arrays at every replay.
+ *
+ * d_status[i] (device, nwindows words, or NULL): window * elem_size; or -71 for
+ * a window that is not decoded (its bytes of `out` stay untouched) -- d_ids[i]
+ * outside [0, count), window above that stream's size, d_starts[i] outside [0,
+ * size - window], or a stream of FEWER THAN Mw BLOCKS: such a stream takes no
+ * window of this length (one shape per call; decode it whole, or with the
+ * single-stream entry); or -91 for a stream whose rebuilt index failed; or the
+ * code of the highest failing block among those that hold the window's
+ * elements; or -91 when the window reaches a verbatim tail that is not inside
+ * its stream.  *d_result: -71 when any window was not decoded, else the status
+ * of the highest-numbered failing window, else nwindows * window * elem_size.
+ * When the set's header does not carry the call's count, elem_size, block_size
+ * and nb_max, every window is -71 and no stream is read.
+ *
+ * Returns 0 once enqueued (nwindows == 0 or window == 0: *d_result = 0).  Host
+ * errors: -81; -71 for window > max_size, nwindows * ((window + block_size - 2)
+ * / block_size + 1) >= 2^31, a block above the LDS decoder's size, a workspace
+ * that is too small or not 256-byte aligned, d_set NULL or not 256-byte
+ * aligned; -70 without a device. */
+size_t bshuf_lz4_stream_set_dev_bytes(const size_t* sizes, size_t count, size_t elem_size, size_t block_size);
+size_t bshuf_lz4_stream_set_dev_workspace(const size_t* in_nbytes, const size_t* sizes, size_t count,
+                                          size_t elem_size, size_t block_size);
+int64_t bshuf_lz4_stream_set_dev(const void* const* ins, const size_t* in_nbytes, const size_t* sizes,
+                                 size_t count, size_t elem_size, size_t block_size,
+                                 const uint64_t* const* block_offsets, void* d_set, size_t set_bytes,
+                                 void* ws, size_t ws_bytes, int64_t* d_status, void* stream);
+size_t bshuf_decompress_lz4_windows_set_dev_workspace(size_t max_size, size_t elem_size, size_t block_size,
+                                                      size_t nwindows, size_t window);
+int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, size_t max_size,
+                                             size_t elem_size, size_t block_size, const int64_t* d_ids,
+                                             const int64_t* d_starts, size_t nwindows, size_t window,
+                                             void* out, void* ws, size_t ws_bytes, int64_t* d_result,
+                                             int64_t* d_status, void* stream);
+
 /* ---- batched device entry points (additive) ----
  *
  * `count` independent framed streams per call, all with the same elem_size and
