@@ -329,6 +329,53 @@ def decompress_lz4_range_dev(buf, size, dtype, start, count, **kw):
     return r if kw.get("sync", True) is False else r[0]
 
 
+def _windows_dev(call, device, whose, index, dtype, window, out, workspace, result, status, sync, elem_size,
+                 holds=None):
+    """What the window decodes of one stream and of a set share.  `index`:
+    (name, tensor) pairs, the device tensors with one entry per window each;
+    `device`: where they must live, called the "`whose` device" in messages.
+    `holds`: the element size the set was built with.  call(es, K, window, out,
+    ws, ws_bytes, result, status) makes the library call with these arguments
+    of its own among the others and returns its code."""
+    torch = _torch()
+    for name, t in index:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+                and t.device == device):
+            raise ValueError("%s must be a contiguous int64 tensor on the %s device" % (name, whose))
+    counts = [t.numel() for _, t in index]
+    if len(set(counts)) > 1:
+        raise ValueError("%s need one entry per window (%s)" % (" and ".join(name for name, _ in index),
+                                                                " and ".join("%d" % n for n in counts)))
+    K, window = counts[-1], int(window)
+    if window < 0:
+        raise ValueError("window must be >= 0, not %d" % window)
+    if out is None:
+        if elem_size is None:
+            out = torch.empty((K, window), dtype=dtype, device=device)
+        else:
+            out = torch.empty((K, window * int(elem_size)), dtype=torch.uint8, device=device)
+    es = out.element_size() if elem_size is None else int(elem_size)
+    if holds is not None and es != holds:
+        raise ValueError("the set holds %d-byte elements, not %d-byte ones" % (holds, es))
+    if out.numel() * out.element_size() < K * window * es:
+        raise ValueError("out holds %d bytes, the windows need %d"
+                         % (out.numel() * out.element_size(), K * window * es))
+    if status is not None and (status.dtype != torch.int64 or status.numel() < K):
+        raise ValueError("status must be an int64 tensor of %d entries" % K)
+    if result is None:
+        result = torch.empty(1, dtype=torch.int64, device=device)
+    ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+    wsb = workspace.numel() if workspace is not None else 0
+    stp = _dptr(status) if status is not None else None
+    _check(call(es, K, window, _dptr(out), ws, wsb, _dptr(result), stp))
+    if not sync:
+        return out, result
+    count = int(result.item())
+    if count < 0:
+        _fail(count)
+    return out
+
+
 def decompress_lz4_windows_workspace(in_nbytes, size, elem_size, nwindows, window, block_size=0,
                                      device=None):
     """A workspace for decompress_lz4_windows_dev of `nwindows` windows of
@@ -356,39 +403,12 @@ def decompress_lz4_windows_dev(buf, size, dtype, starts, window, block_size=0, o
     window] (that window's part of `out` is left as it was), or the code of a
     failing block it touches.  `offsets`: the stream's block index; without it
     the index is rebuilt from the whole stream."""
-    torch = _torch()
-    if not (isinstance(starts, torch.Tensor) and starts.is_cuda and starts.dtype == torch.int64
-            and starts.is_contiguous() and starts.device == buf.device):
-        raise ValueError("starts must be a contiguous int64 tensor on the stream's device")
-    K, window = starts.numel(), int(window)
-    if window < 0:
-        raise ValueError("window must be >= 0, not %d" % window)
-    if out is None:
-        if elem_size is None:
-            out = torch.empty((K, window), dtype=dtype, device=buf.device)
-        else:
-            out = torch.empty((K, window * int(elem_size)), dtype=torch.uint8, device=buf.device)
-    es = out.element_size() if elem_size is None else int(elem_size)
-    if out.numel() * out.element_size() < K * window * es:
-        raise ValueError("out holds %d bytes, the windows need %d"
-                         % (out.numel() * out.element_size(), K * window * es))
-    if status is not None and (status.dtype != torch.int64 or status.numel() < K):
-        raise ValueError("status must be an int64 tensor of %d entries" % K)
-    if result is None:
-        result = torch.empty(1, dtype=torch.int64, device=buf.device)
-    ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
-    wsb = workspace.numel() if workspace is not None else 0
-    offp = _dptr(offsets) if offsets is not None else None
-    stp = _dptr(status) if status is not None else None
-    _check(lib.bshuf_decompress_lz4_windows_dev(_dptr(buf), buf.numel(), int(size), es, block_size,
-                                                _dptr(starts), K, window, _dptr(out), ws, wsb,
-                                                _dptr(result), stp, offp, _stream(stream)))
-    if not sync:
-        return out, result
-    count = int(result.item())
-    if count < 0:
-        _fail(count)
-    return out
+    def call(es, K, window, *ptrs):
+        offp = _dptr(offsets) if offsets is not None else None
+        return lib.bshuf_decompress_lz4_windows_dev(_dptr(buf), buf.numel(), int(size), es, block_size,
+                                                    _dptr(starts), K, window, *ptrs, offp, _stream(stream))
+    return _windows_dev(call, buf.device, "stream's", [("starts", starts)], dtype, window, out, workspace,
+                        result, status, sync, elem_size)
 
 
 class StreamSet:
@@ -473,44 +493,12 @@ def decompress_lz4_windows_set_dev(sset, dtype, ids, starts, window, out=None, w
     blocks of the largest stream) blocks (that window's part of `out` is left as
     it was); -91 for a stream whose rebuilt index failed; or the code of a
     failing block the window touches."""
-    torch = _torch()
-    for name, t in (("ids", ids), ("starts", starts)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
-                and t.device == sset.device):
-            raise ValueError("%s must be a contiguous int64 tensor on the set's device" % name)
-    if ids.numel() != starts.numel():
-        raise ValueError("ids and starts need one entry per window (%d and %d)" % (ids.numel(), starts.numel()))
-    K, window = starts.numel(), int(window)
-    if window < 0:
-        raise ValueError("window must be >= 0, not %d" % window)
-    if out is None:
-        if elem_size is None:
-            out = torch.empty((K, window), dtype=dtype, device=sset.device)
-        else:
-            out = torch.empty((K, window * int(elem_size)), dtype=torch.uint8, device=sset.device)
-    es = out.element_size() if elem_size is None else int(elem_size)
-    if es != sset.elem_size:
-        raise ValueError("the set holds %d-byte elements, not %d-byte ones" % (sset.elem_size, es))
-    if out.numel() * out.element_size() < K * window * es:
-        raise ValueError("out holds %d bytes, the windows need %d"
-                         % (out.numel() * out.element_size(), K * window * es))
-    if status is not None and (status.dtype != torch.int64 or status.numel() < K):
-        raise ValueError("status must be an int64 tensor of %d entries" % K)
-    if result is None:
-        result = torch.empty(1, dtype=torch.int64, device=sset.device)
-    ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
-    wsb = workspace.numel() if workspace is not None else 0
-    stp = _dptr(status) if status is not None else None
-    _check(lib.bshuf_decompress_lz4_windows_set_dev(_dptr(sset.table), sset.count, sset.max_size, es,
-                                                    sset.block_size, _dptr(ids), _dptr(starts), K, window,
-                                                    _dptr(out), ws, wsb, _dptr(result), stp,
-                                                    _stream(stream)))
-    if not sync:
-        return out, result
-    count = int(result.item())
-    if count < 0:
-        _fail(count)
-    return out
+    def call(es, K, window, *ptrs):
+        return lib.bshuf_decompress_lz4_windows_set_dev(_dptr(sset.table), sset.count, sset.max_size, es,
+                                                        sset.block_size, _dptr(ids), _dptr(starts), K, window,
+                                                        *ptrs, _stream(stream))
+    return _windows_dev(call, sset.device, "set's", [("ids", ids), ("starts", starts)], dtype, window, out,
+                        workspace, result, status, sync, elem_size, holds=sset.elem_size)
 
 
 def block_index_dev(buf, size, elem_size, block_size=0, workspace=None, stream=None):

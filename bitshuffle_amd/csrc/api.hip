@@ -691,6 +691,35 @@ int64_t plan_ranges(const Plan& p, size_t size, size_t in_nbytes, const size_t* 
     return 0;
 }
 
+// The buffers of the whole-stream index rebuild of a range or window call
+// (x.offs: the block index), carved whether or not the caller supplies an
+// index: one size per call shape.
+void carve_index(Carver& c, const Plan& p, int64_t blocks_end, DecodeBufs& x) {
+    x.chunk = index_chunk_bytes(p.L);
+    x.nchunks = blocks_end > 0 ? (blocks_end + x.chunk - 1) / x.chunk : 0;
+    x.offs = c.take<uint64_t>((size_t)p.nb * 8 + 8);
+    x.exits = c.take<int64_t>((size_t)x.nchunks * 8 + 8);
+    x.cnt = c.take<uint64_t>((size_t)(x.nchunks + 1) * 8);
+    x.base = c.take<uint64_t>((size_t)(x.nchunks + 1) * 8);
+    x.idx_err = c.take<int64_t>(8);
+    x.scan_tmp_bytes = decode_scan_tmp_bytes(x.nchunks);
+    x.scan_tmp = c.take<void>(x.scan_tmp_bytes + 8);
+}
+
+// The stream of a range or window call as its kernels see it, with the caller's
+// block index, or, without one, the index that the rebuild launched here writes
+// into idx; idx_err is then the rebuild's error word, else nullptr.
+hipError_t stream_with_index(const uint8_t* in, size_t in_nbytes, int64_t blocks_end, const Plan& p,
+                             const uint64_t* block_offsets, const DecodeBufs& idx, hipStream_t s,
+                             RangeStream& st, const int64_t*& idx_err) {
+    st = RangeStream{in, (int64_t)in_nbytes, block_offsets, p.nb, p.tail, (uint32_t)lz4_bound(p.L.bs * p.L.E)};
+    idx_err = nullptr;
+    if (block_offsets) return hipSuccess;
+    st.offs = idx.offs;
+    idx_err = idx.idx_err;
+    return launch_index(in, blocks_end, p.L, idx, s, nullptr, (int64_t)in_nbytes, p.tail);
+}
+
 struct RangeBufs {
     Seg* segs;          // one per decode piece; behind them (16-aligned) the RangePiece table
     RangePiece* pcs;
@@ -703,8 +732,6 @@ struct RangeBufs {
     DecodeBufs idx;     // index rebuild of the whole stream (offs: its block index)
 };
 
-// (the index rebuild's buffers are carved whether or not the caller supplies an
-// index: one size per call shape)
 size_t range_ws(const Plan& p, const RangePlan& rp, int64_t blocks_end, RangeBufs* b, uint8_t* base) {
     Carver c{base};
     RangeBufs x{};
@@ -725,17 +752,7 @@ size_t range_ws(const Plan& p, const RangePlan& rp, int64_t blocks_end, RangeBuf
     x.res = c.take<int64_t>(np * 8 + 8);
     x.slot = ((int64_t)p.L.bs * p.L.E + 15) & ~(int64_t)15;
     x.slots = c.take<uint8_t>((size_t)(rp.nedge * x.slot));
-    {
-        x.idx.chunk = index_chunk_bytes(p.L);
-        x.idx.nchunks = blocks_end > 0 ? (blocks_end + x.idx.chunk - 1) / x.idx.chunk : 0;
-        x.idx.offs = c.take<uint64_t>((size_t)p.nb * 8 + 8);
-        x.idx.exits = c.take<int64_t>((size_t)x.idx.nchunks * 8 + 8);
-        x.idx.cnt = c.take<uint64_t>((size_t)(x.idx.nchunks + 1) * 8);
-        x.idx.base = c.take<uint64_t>((size_t)(x.idx.nchunks + 1) * 8);
-        x.idx.idx_err = c.take<int64_t>(8);
-        x.idx.scan_tmp_bytes = decode_scan_tmp_bytes(x.idx.nchunks);
-        x.idx.scan_tmp = c.take<void>(x.idx.scan_tmp_bytes + 8);
-    }
+    carve_index(c, p, blocks_end, x.idx);
     if (b) *b = x;
     return c.off;
 }
@@ -770,7 +787,6 @@ int64_t bshuf_decompress_lz4_ranges_dev(const void* in, size_t in_nbytes, size_t
     if (np == 0) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
     int64_t cb = (int64_t)in_nbytes - p.tail;
     if (cb < 0) cb = 0;
-    const bool need_index = block_offsets == nullptr;
     const size_t need = range_ws(p, rp, cb, nullptr, nullptr);
     DevBuf own;
     r = get_ws(ws, ws_bytes, need, own, s);
@@ -835,15 +851,9 @@ int64_t bshuf_decompress_lz4_ranges_dev(const void* in, size_t in_nbytes, size_t
     }
     if (stage_upload(tab.data(), tab.size(), b.segs, s) != hipSuccess) return kErrHip;
 
-    const uint64_t* offs = block_offsets;
-    const int64_t* idx_err = nullptr;
-    if (need_index) {
-        if (launch_index(i8, cb, p.L, b.idx, s, nullptr, (int64_t)in_nbytes, p.tail) != hipSuccess)
-            return kErrHip;
-        offs = b.idx.offs;
-        idx_err = b.idx.idx_err;
-    }
-    const RangeStream st{i8, (int64_t)in_nbytes, offs, p.nb, p.tail, (uint32_t)lz4_bound(p.L.bs * p.L.E)};
+    RangeStream st;
+    const int64_t* idx_err;
+    if (stream_with_index(i8, in_nbytes, cb, p, block_offsets, b.idx, s, st, idx_err) != hipSuccess) return kErrHip;
     if (rp.large) {
         // blocks above the LDS decoder's size: one piece at a time through the
         // whole decode's route, its index being the stream's from block b0 on
@@ -852,7 +862,7 @@ int64_t bshuf_decompress_lz4_ranges_dev(const void* in, size_t in_nbytes, size_t
             L.nfull = hsegs[i].nfull;
             L.last = hsegs[i].last;
             DecodeBufs d = b.d;
-            d.offs = const_cast<uint64_t*>(offs) + hpcs[i].b0;
+            d.offs = const_cast<uint64_t*>(st.offs) + hpcs[i].b0;
             d.idx_err = nullptr;
             if (launch_decode(i8, (int64_t)in_nbytes, hsegs[i].out, L, 0, d, b.res + i, s) != hipSuccess)
                 return kErrHip;
@@ -894,7 +904,8 @@ int64_t bshuf_decompress_lz4_ranges_dev(const void* in, size_t in_nbytes, size_t
 
 namespace {
 
-// What the host knows of a window call: everything but the starts.
+// What the host knows of a window call, over one stream or over a set:
+// everything but the starts (and the stream indices).
 struct WindowShape {
     int64_t K = 0, window = 0;
     int64_t Mw = 0;         // work blocks per window
@@ -902,11 +913,16 @@ struct WindowShape {
     bool shared_seq = false;  // whole decode's area indexed by stream offset, when that is smaller
     int64_t pw = 0;         // words of one private area
     int64_t slot = 0;       // bytes of one staging area
+    bool set = false;       // over a set: a stream index per window, no index rebuild
 };
 
-int64_t window_shape(const Plan& p, size_t size, size_t in_nbytes, size_t nwindows, size_t window,
+// p, size: of the stream, or (set) of the set's largest stream, and then the
+// token positions are private: offsets of different streams collide in a shared
+// area, and in_nbytes is not looked at.
+int64_t window_shape(const Plan& p, size_t size, size_t in_nbytes, size_t nwindows, size_t window, bool set,
                      WindowShape& w) {
     const Layout& L = p.L;
+    w.set = set;
     if (window > size) return kErrUnsupported;
     const uint64_t M = window ? ((uint64_t)window + L.bs - 2) / L.bs + 1 : 1;
     if (nwindows >= ((uint64_t)1 << 31) || M >= ((uint64_t)1 << 31) || nwindows * M >= ((uint64_t)1 << 31))
@@ -919,7 +935,7 @@ int64_t window_shape(const Plan& p, size_t size, size_t in_nbytes, size_t nwindo
     const int64_t maxlen = lz4_bound(L.bs * L.E);
     w.pw = w.Mw * (4 + maxlen) / 3 + 80;
     const int64_t shared_words = (int64_t)in_nbytes / 3 + 80;
-    w.shared_seq = shared_words < w.K * w.pw;
+    w.shared_seq = !set && shared_words < w.K * w.pw;
     w.seq_words = w.shared_seq ? shared_words : w.K * w.pw;
     w.slot = (w.Mw * (int64_t)L.bs * L.E + 15) & ~(int64_t)15;
     return 0;
@@ -934,12 +950,13 @@ struct WindowBufs {
     int64_t* res;    // one per window: its Seg's result
     int64_t* wstat;  // one per window, when the caller passes no d_status
     uint8_t* slots;  // staging areas
-    DecodeBufs idx;  // index rebuild of the whole stream (offs: its block index)
+    DecodeBufs idx;  // one stream: index rebuild of the whole stream (offs: its block index)
+    int32_t* sidx;   // set: per window, its stream
 };
 
 // K Seg, RangePiece and WindowTail records, K * Mw work blocks (map, offsets,
 // status), the token positions, K * Mw staging blocks, and the index rebuild's
-// buffers (carved whether or not the caller supplies an index).
+// buffers (one stream) or the windows' stream indices (set).
 size_t window_ws(const Plan& p, const WindowShape& w, int64_t blocks_end, WindowBufs* b, uint8_t* base) {
     Carver c{base};
     WindowBufs x{};
@@ -957,19 +974,62 @@ size_t window_ws(const Plan& p, const WindowShape& w, int64_t blocks_end, Window
     x.res = c.take<int64_t>(K * 8 + 8);
     x.wstat = c.take<int64_t>(K * 8 + 8);
     x.slots = c.take<uint8_t>(K * (size_t)w.slot);
-    {
-        x.idx.chunk = index_chunk_bytes(p.L);
-        x.idx.nchunks = blocks_end > 0 ? (blocks_end + x.idx.chunk - 1) / x.idx.chunk : 0;
-        x.idx.offs = c.take<uint64_t>((size_t)p.nb * 8 + 8);
-        x.idx.exits = c.take<int64_t>((size_t)x.idx.nchunks * 8 + 8);
-        x.idx.cnt = c.take<uint64_t>((size_t)(x.idx.nchunks + 1) * 8);
-        x.idx.base = c.take<uint64_t>((size_t)(x.idx.nchunks + 1) * 8);
-        x.idx.idx_err = c.take<int64_t>(8);
-        x.idx.scan_tmp_bytes = decode_scan_tmp_bytes(x.idx.nchunks);
-        x.idx.scan_tmp = c.take<void>(x.idx.scan_tmp_bytes + 8);
-    }
+    if (w.set)
+        x.sidx = c.take<int32_t>(K * 4 + 4);
+    else
+        carve_index(c, p, blocks_end, x.idx);
     if (b) *b = x;
     return c.off;
+}
+
+// What the two window entry points share, from the workspace to the result.
+// make_source(b): the call's source, with what of it lies in the workspace.
+// worklist(src, c, b, idx_err): the source's index rebuild, if it has one
+// (idx_err: its error word), and then, when there are blocks (c.Mw > 0), the
+// zeroed per-window error words of the decode and the work list.
+extern "C++" template <class MakeSource, class Worklist>
+int64_t window_decode(const Plan& p, const WindowShape& w, int64_t blocks_end, size_t need,
+                      const int64_t* d_starts, void* out, void* ws, size_t ws_bytes, int64_t* d_result,
+                      int64_t* d_status, hipStream_t s, MakeSource make_source, Worklist worklist) {
+    DevBuf own;
+    const int64_t r = get_ws(ws, ws_bytes, need, own, s);
+    if (r) return r;
+    WindowBufs b;
+    window_ws(p, w, blocks_end, &b, (uint8_t*)ws);
+    const int K = (int)w.K;
+    int64_t* wstat = d_status ? d_status : b.wstat;
+
+    auto src = make_source(b);
+    WindowCall c{};
+    c.starts = d_starts;
+    c.out = (uint8_t*)out;
+    c.slots = b.slots;
+    c.res = b.res;
+    c.window = w.window;
+    c.wbytes = w.window * p.L.E;
+    c.slot = w.slot;
+    c.Mw = w.Mw;
+    c.seq_words = w.shared_seq ? -1 : w.pw;
+    c.bs = p.L.bs;
+    c.E = p.L.E;
+    c.K = K;
+    if (launch_window_plan(src, c, b.segs, b.pcs, b.wt, s) != hipSuccess) return kErrHip;
+    const int64_t* idx_err = nullptr;
+    if (worklist(src, c, b, idx_err) != hipSuccess) return kErrHip;
+    if (w.Mw > 0) {
+        // every window's staging area is 16-byte aligned: one scan and one
+        // decode launch over all K * Mw work blocks, no host copy of the table
+        Layout L = p.L;
+        L.nfull = w.K * w.Mw;
+        L.last = 0;
+        if (launch_seg_map(b.segs, K, b.blk_seg, false, s) != hipSuccess ||
+            launch_decode_batch(b.segs, nullptr, K, b.blk_seg, L, b.d, s) != hipSuccess)
+            return kErrHip;
+    }
+    if (launch_window_gather(src, c, b.pcs, b.wt, b.d.status, wstat, s) != hipSuccess ||
+        launch_window_reduce(wstat, b.wt, K, idx_err, w.K * c.wbytes, d_result, s) != hipSuccess)
+        return kErrHip;
+    return 0;
 }
 
 }  // namespace
@@ -978,7 +1038,7 @@ size_t bshuf_decompress_lz4_windows_dev_workspace(size_t in_nbytes, size_t size,
                                                   size_t block_size, size_t nwindows, size_t window) {
     Plan p;
     WindowShape w;
-    if (make_plan(size, elem_size, block_size, p) || window_shape(p, size, in_nbytes, nwindows, window, w))
+    if (make_plan(size, elem_size, block_size, p) || window_shape(p, size, in_nbytes, nwindows, window, false, w))
         return 0;
     const int64_t cb = (int64_t)in_nbytes - p.tail;
     return window_ws(p, w, cb > 0 ? cb : 0, nullptr, nullptr);
@@ -993,7 +1053,7 @@ int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_
     int64_t r = make_plan(size, elem_size, block_size, p);
     if (r) return r;
     WindowShape w;
-    r = window_shape(p, size, in_nbytes, nwindows, window, w);
+    r = window_shape(p, size, in_nbytes, nwindows, window, false, w);
     if (r) return r;
     int64_t cb = (int64_t)in_nbytes - p.tail;
     if (cb < 0) cb = 0;
@@ -1002,57 +1062,18 @@ int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_
     if (!have_device()) return kErrHip;
     hipStream_t s = (hipStream_t)stream;
     if (nwindows == 0 || window == 0) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
-    DevBuf own;
-    r = get_ws(ws, ws_bytes, need, own, s);
-    if (r) return r;
-    WindowBufs b;
-    window_ws(p, w, cb, &b, (uint8_t*)ws);
     const uint8_t* i8 = (const uint8_t*)in;
-    const int K = (int)w.K;
-    int64_t* wstat = d_status ? d_status : b.wstat;
-
-    WindowCall c{};
-    c.in = i8;
-    c.starts = d_starts;
-    c.out = (uint8_t*)out;
-    c.slots = b.slots;
-    c.res = b.res;
-    c.size = (int64_t)size;
-    c.window = w.window;
-    c.wbytes = w.window * p.L.E;
-    c.slot = w.slot;
-    c.Mw = w.Mw;
-    c.seq_words = w.shared_seq ? -1 : w.pw;
-    c.bs = p.L.bs;
-    c.E = p.L.E;
-    c.K = K;
-    if (launch_window_plan(c, b.segs, b.pcs, b.wt, s) != hipSuccess) return kErrHip;
-
-    const uint64_t* offs = block_offsets;
-    const int64_t* idx_err = nullptr;
-    if (!block_offsets) {
-        if (launch_index(i8, cb, p.L, b.idx, s, nullptr, (int64_t)in_nbytes, p.tail) != hipSuccess)
-            return kErrHip;
-        offs = b.idx.offs;
-        idx_err = b.idx.idx_err;
-    }
-    const RangeStream st{i8, (int64_t)in_nbytes, offs, p.nb, p.tail, (uint32_t)lz4_bound(p.L.bs * p.L.E)};
-    if (w.Mw > 0) {
-        // every window's staging area is 16-byte aligned: one scan and one
-        // decode launch over all K * Mw work blocks, no host copy of the table
-        Layout L = p.L;
-        L.nfull = w.K * w.Mw;
-        L.last = 0;
-        if (dev_fill(b.d.idx_err, 0, (size_t)K * 8, s) != hipSuccess ||
-            launch_range_worklist(st, b.segs, b.pcs, K, K, 0, w.Mw, b.d.offs, s) != hipSuccess ||
-            launch_seg_map(b.segs, K, b.blk_seg, false, s) != hipSuccess ||
-            launch_decode_batch(b.segs, nullptr, K, b.blk_seg, L, b.d, s) != hipSuccess)
-            return kErrHip;
-    }
-    if (launch_window_gather(st, c, b.pcs, b.wt, b.d.status, wstat, s) != hipSuccess ||
-        launch_window_reduce(wstat, b.wt, K, idx_err, w.K * c.wbytes, d_result, s) != hipSuccess)
-        return kErrHip;
-    return 0;
+    return window_decode(
+        p, w, cb, need, d_starts, out, ws, ws_bytes, d_result, d_status, s,
+        // the plan reads the stream's address and size only: the index comes behind it
+        [&](const WindowBufs&) { return WindowStream{RangeStream{i8}, (int64_t)size}; },
+        [&](WindowStream& src, const WindowCall& c, const WindowBufs& b, const int64_t*& idx_err) {
+            hipError_t e = stream_with_index(i8, in_nbytes, cb, p, block_offsets, b.idx, s, src.st, idx_err);
+            if (e != hipSuccess || c.Mw <= 0) return e;
+            e = dev_fill(b.d.idx_err, 0, (size_t)c.K * 8, s);
+            if (e != hipSuccess) return e;
+            return launch_range_worklist(src.st, b.segs, b.pcs, c.K, c.K, 0, c.Mw, b.d.offs, s);
+        });
 }
 
 // ---------------------------------------------------------------------------
@@ -1214,76 +1235,13 @@ int64_t bshuf_lz4_stream_set_dev(const void* const* ins, const size_t* in_nbytes
     return 0;
 }
 
-namespace {
-
-// What the host knows of a window call over a set: everything but ids and starts.
-struct WindowSetShape {
-    int64_t K = 0, window = 0;
-    int64_t nb_max = 0;
-    int64_t Mw = 0;    // work blocks per window
-    int64_t pw = 0;    // words of one window's token-position area
-    int64_t slot = 0;  // bytes of one staging area
-};
-
-int64_t window_set_shape(const Plan& p, size_t max_size, size_t nwindows, size_t window, WindowSetShape& w) {
-    const Layout& L = p.L;
-    if (window > max_size) return kErrUnsupported;
-    const uint64_t M = window ? ((uint64_t)window + L.bs - 2) / L.bs + 1 : 1;
-    if (nwindows >= ((uint64_t)1 << 31) || M >= ((uint64_t)1 << 31) || nwindows * M >= ((uint64_t)1 << 31))
-        return kErrUnsupported;
-    if ((int64_t)L.bs * L.E > max_lds_decode_bytes()) return kErrUnsupported;
-    w.K = (int64_t)nwindows;
-    w.window = (int64_t)window;
-    w.nb_max = p.nb;
-    w.Mw = window ? window_blocks((int64_t)max_size, L.bs, (int64_t)window) : 0;
-    w.pw = w.Mw * (4 + (int64_t)lz4_bound(L.bs * L.E)) / 3 + 80;
-    w.slot = (w.Mw * (int64_t)L.bs * L.E + 15) & ~(int64_t)15;
-    return 0;
-}
-
-struct WindowSetBufs {
-    Seg* segs;
-    RangePiece* pcs;
-    WindowTail* wt;
-    int32_t* sidx;   // per window: its stream
-    uint32_t* blk_seg;
-    DecodeBufs d;    // offs: the work list; idx_err: zeros, one per window
-    int64_t* res;    // one per window: its Seg's result
-    int64_t* wstat;  // one per window, when the caller passes no d_status
-    uint8_t* slots;  // staging areas
-};
-
-size_t window_set_ws(const WindowSetShape& w, WindowSetBufs* b, uint8_t* base) {
-    Carver c{base};
-    WindowSetBufs x{};
-    const size_t K = (size_t)w.K, nwork = (size_t)(w.K * w.Mw);
-    x.segs = c.take<Seg>(K * sizeof(Seg));
-    x.pcs = c.take<RangePiece>(K * sizeof(RangePiece));
-    x.wt = c.take<WindowTail>(K * sizeof(WindowTail));
-    x.sidx = c.take<int32_t>(K * 4 + 4);
-    x.blk_seg = c.take<uint32_t>(nwork * 4 + 4);
-    x.d.offs = c.take<uint64_t>(nwork * 8 + 8);
-    x.d.status = c.take<int64_t>(nwork * 8 + 8);
-    x.d.seq = c.take<uint32_t>(K * (size_t)w.pw * 4);
-    x.d.idx_err = c.take<int64_t>(K * 8 + 8);
-    x.d.bad = c.take<long long>(K * 8 + 8);
-    x.d.tickets = c.take<uint32_t>(kTicketSetBytes);
-    x.res = c.take<int64_t>(K * 8 + 8);
-    x.wstat = c.take<int64_t>(K * 8 + 8);
-    x.slots = c.take<uint8_t>(K * (size_t)w.slot);
-    if (b) *b = x;
-    return c.off;
-}
-
-}  // namespace
-
 size_t bshuf_decompress_lz4_windows_set_dev_workspace(size_t max_size, size_t elem_size, size_t block_size,
                                                       size_t nwindows, size_t window) {
     Plan p;
-    WindowSetShape w;
-    if (make_plan(max_size, elem_size, block_size, p) || window_set_shape(p, max_size, nwindows, window, w))
+    WindowShape w;
+    if (make_plan(max_size, elem_size, block_size, p) || window_shape(p, max_size, 0, nwindows, window, true, w))
         return 0;
-    return window_set_ws(w, nullptr, nullptr);
+    return window_ws(p, w, 0, nullptr, nullptr);
 }
 
 int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
@@ -1294,60 +1252,33 @@ int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, si
     Plan p;
     int64_t r = make_plan(max_size, elem_size, block_size, p);
     if (r) return r;
-    WindowSetShape w;
-    r = window_set_shape(p, max_size, nwindows, window, w);
+    WindowShape w;
+    r = window_shape(p, max_size, 0, nwindows, window, true, w);
     if (r) return r;
     if (count > (size_t)INT32_MAX) return kErrUnsupported;
-    const size_t need = window_set_ws(w, nullptr, nullptr);
+    const size_t need = window_ws(p, w, 0, nullptr, nullptr);
     if (ws && (ws_bytes < need || ((uintptr_t)ws & 255))) return kErrUnsupported;
     if (!d_set || ((uintptr_t)d_set & 255)) return kErrUnsupported;
     if (!have_device()) return kErrHip;
     hipStream_t s = (hipStream_t)stream;
     if (nwindows == 0 || window == 0) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
-    DevBuf own;
-    r = get_ws(ws, ws_bytes, need, own, s);
-    if (r) return r;
-    WindowSetBufs b;
-    window_set_ws(w, &b, (uint8_t*)ws);
-    const int K = (int)w.K;
-    int64_t* wstat = d_status ? d_status : b.wstat;
-
-    WindowSetCall c{};
-    c.hdr = (const StreamSetHeader*)d_set;
-    c.recs = (const StreamSetRec*)((const uint8_t*)d_set + kStreamSetRecs);
-    c.ids = d_ids;
-    c.starts = d_starts;
-    c.out = (uint8_t*)out;
-    c.slots = b.slots;
-    c.res = b.res;
-    c.sidx = b.sidx;
-    c.count = (int64_t)count;
-    c.nb_max = w.nb_max;
-    c.window = w.window;
-    c.wbytes = w.window * p.L.E;
-    c.slot = w.slot;
-    c.Mw = w.Mw;
-    c.seq_words = w.pw;
-    c.bs = p.L.bs;
-    c.E = p.L.E;
-    c.K = K;
-    if (launch_window_set_plan(c, b.segs, b.pcs, b.wt, s) != hipSuccess) return kErrHip;
-    if (w.Mw > 0) {
-        // as the window decode of one stream: one scan and one decode launch
-        // over all K * Mw work blocks, no host copy of the table
-        Layout L = p.L;
-        L.nfull = w.K * w.Mw;
-        L.last = 0;
-        if (dev_fill(b.d.idx_err, 0, (size_t)K * 8, s) != hipSuccess ||
-            launch_window_set_worklist(c, b.segs, b.pcs, b.d.offs, s) != hipSuccess ||
-            launch_seg_map(b.segs, K, b.blk_seg, false, s) != hipSuccess ||
-            launch_decode_batch(b.segs, nullptr, K, b.blk_seg, L, b.d, s) != hipSuccess)
-            return kErrHip;
-    }
-    if (launch_window_set_gather(c, b.pcs, b.wt, b.d.status, wstat, s) != hipSuccess ||
-        launch_window_reduce(wstat, b.wt, K, nullptr, w.K * c.wbytes, d_result, s) != hipSuccess)
-        return kErrHip;
-    return 0;
+    return window_decode(
+        p, w, 0, need, d_starts, out, ws, ws_bytes, d_result, d_status, s,
+        [&](const WindowBufs& b) {
+            return WindowSet{(const StreamSetHeader*)d_set,
+                             (const StreamSetRec*)((const uint8_t*)d_set + kStreamSetRecs),
+                             d_ids,
+                             b.sidx,
+                             (int64_t)count,
+                             p.nb};
+        },
+        // (the set's indexes were made by its build: nothing to rebuild)
+        [&](const WindowSet& src, const WindowCall& c, const WindowBufs& b, const int64_t*&) {
+            if (c.Mw <= 0) return hipSuccess;
+            const hipError_t e = dev_fill(b.d.idx_err, 0, (size_t)c.K * 8, s);
+            if (e != hipSuccess) return e;
+            return launch_window_set_worklist(src, c, b.segs, b.pcs, b.d.offs, s);
+        });
 }
 
 int64_t bshuf_synth_fill_dev(void* out, size_t n_elem, int gen, uint64_t first, uint64_t seed,

@@ -292,61 +292,52 @@ hipError_t launch_range_reduce(const int64_t* res, int np, const int64_t* idx_er
                                int64_t* result, hipStream_t s);
 
 // ---- window decode (lz4_window.hip) --------------------------------------
-// K windows of the same length at DEVICE-held starts
-// (bshuf_decompress_lz4_windows_dev).  With the length and K known on the host,
-// every table of the range decode has a host-known shape (window_plan.h): window
-// i is one Seg of Mw consecutive blocks, decoded back to back into staging area
-// i, work blocks [i * Mw, (i + 1) * Mw).  k_window_plan writes the tables from
-// the starts; k_range_worklist, launch_seg_map and launch_decode_batch run as
-// in the range decode; k_window_gather copies each window's clip of its staging
-// area and its span of the verbatim tail to the output; k_window_reduce makes
-// the call's result.  No host table depends on the starts.
+// K windows of the same length at DEVICE-held starts, in one stream
+// (bshuf_decompress_lz4_windows_dev) or each in a stream of a set
+// (bshuf_decompress_lz4_windows_set_dev, below).  With the length and K known
+// on the host, every table of the range decode has a host-known shape
+// (window_plan.h): window i is one Seg of Mw consecutive blocks of its stream,
+// decoded back to back into staging area i, work blocks [i * Mw, (i + 1) * Mw).
+// k_window_plan writes the tables from the starts; the work list,
+// launch_seg_map and launch_decode_batch run as in the range decode;
+// k_window_gather copies each window's clip of its staging area and its span of
+// the verbatim tail to the output; k_window_reduce makes the call's result.  No
+// host table depends on the starts.  Where a window's stream comes from is the
+// call's SOURCE, a template parameter of the plan and gather kernels: WindowStream
+// (the one stream of the call) or WindowSet.
+//
+// A stream set (bshuf_lz4_stream_set_dev) is a device table of `count` framed
+// streams that share E and bs: a header, one record per stream, and the block
+// indexes the build rebuilt (a stream whose index the caller supplied keeps the
+// caller's pointer).  Window i of a call over it is elements [starts[i],
+// starts[i] + L) of stream ids[i], both DEVICE arrays.  What differs from one
+// stream: Mw = min(M, blocks of the set's largest stream) for every window; a
+// token-position area per window (offsets of different streams collide in a
+// shared one); a work list of its own, k_window_set_worklist, that takes every
+// window's stream from the set.  A bad window (window_plan.h, window_set_plan)
+// decodes blocks [0, Mw) of stream `ref`, which has that many, so the work list
+// stays dense and inside a real stream; nothing of that decode is used.  When
+// the header does not match the call, every window is bad and there is no
+// stream to trust: their work blocks then hold the sentinel offset, which the
+// decoder rejects without reading anything.
 struct WindowTail {
     int64_t lo, n;   // tail span: bytes of the verbatim tail, behind the clip in the window
     int32_t t0, t1;  // work blocks [t0, t1) of the window hold clip bytes
-    int32_t bad;     // the start was out of range
+    int32_t bad;     // the window is refused (-71): start out of range, or (set) no such stream
     int32_t pad_;
 };
 struct WindowCall {
-    const uint8_t* in;      // the stream
     const int64_t* starts;  // device, K element indices
     uint8_t* out;           // window i at out + i * wbytes
     uint8_t* slots;         // staging areas of `slot` bytes (16-aligned)
     int64_t* res;           // per window: its Seg's result
-    int64_t size, window;   // elements
+    int64_t window;         // elements
     int64_t wbytes, slot;
     int64_t Mw;             // work blocks per window
     int64_t seq_words;      // per window, of its own token-position area; -1: the shared area
     int32_t bs, E;
     int32_t K, pad_;
 };
-hipError_t launch_window_plan(const WindowCall& c, Seg* segs, RangePiece* pcs, WindowTail* wt, hipStream_t s);
-// status[i] (wstat): c.wbytes, or -71 (start out of range), the code of the
-// highest failing block that holds clip bytes (dstat: the decode's per-block
-// status; nullptr with res == nullptr: no blocks), or -91 (tail not inside the stream);
-// only windows with c.wbytes are copied.
-hipError_t launch_window_gather(const RangeStream& st, const WindowCall& c, const RangePiece* pcs,
-                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s);
-// *result = -91 when *idx_err (nullptr: an index was supplied) is set, else -71
-// when a start was out of range, else the status of the highest-numbered
-// failing window, else K * wbytes.
-hipError_t launch_window_reduce(const int64_t* wstat, const WindowTail* wt, int K, const int64_t* idx_err,
-                                int64_t total, int64_t* result, hipStream_t s);
-
-// ---- window decode over a set of streams (lz4_window_set.hip) --------------
-// A stream set (bshuf_lz4_stream_set_dev) is a device table of `count` framed
-// streams that share E and bs: a header, one record per stream, and the block
-// indexes the build rebuilt (a stream whose index the caller supplied keeps the
-// caller's pointer).  bshuf_decompress_lz4_windows_set_dev decodes K windows of
-// one length; window i is elements [starts[i], starts[i] + L) of stream ids[i],
-// both DEVICE arrays.  The shape is the window decode's with Mw = min(M, blocks
-// of the set's largest stream) for every window, and a token-position area per
-// window (offsets of different streams collide in a shared one).  A bad window
-// (window_plan.h, window_set_plan) decodes blocks [0, Mw) of stream `ref`, which
-// has that many, so the work list stays dense and inside a real stream; nothing
-// of that decode is used.  When the header does not match the call, every
-// window is bad and there is no stream to trust: their work blocks then hold
-// the sentinel offset, which the decoder rejects without reading anything.
 constexpr uint64_t kStreamSetMagic = 0x3154455346485342ull;  // "BSHFSET1"
 struct StreamSetHeader {
     uint64_t magic;
@@ -365,31 +356,37 @@ static_assert(sizeof(StreamSetHeader) == 64 && sizeof(StreamSetRec) == 64, "stre
 // rec[s].err and status[s] from the index rebuild's error words (0 -> 0, else -91)
 hipError_t launch_stream_set_status(StreamSetRec* recs, const int64_t* idx_err, int64_t* status, int count,
                                     hipStream_t s);
-struct WindowSetCall {
+// The two sources.
+struct WindowStream {
+    RangeStream st;  // (the plan reads st.in only: st.offs may still be under construction)
+    int64_t size;    // elements
+};
+struct WindowSet {
     const StreamSetHeader* hdr;
     const StreamSetRec* recs;
     const int64_t* ids;     // device, K stream indices
-    const int64_t* starts;  // device, K element indices
-    uint8_t* out;           // window i at out + i * wbytes
-    uint8_t* slots;         // staging areas of `slot` bytes (16-aligned)
-    int64_t* res;           // per window: its Seg's result
     int32_t* sidx;          // per window: the stream its blocks come from (-1: none, sentinel offsets)
     int64_t count, nb_max;  // what the call says of the set
-    int64_t window, wbytes, slot;
-    int64_t Mw;             // work blocks per window
-    int64_t seq_words;      // per window, of its own token-position area
-    int32_t bs, E;
-    int32_t K, pad_;
 };
-hipError_t launch_window_set_plan(const WindowSetCall& c, Seg* segs, RangePiece* pcs, WindowTail* wt,
-                                  hipStream_t s);
-// k_range_worklist with every piece's stream taken from the set's record of c.sidx[piece]
-hipError_t launch_window_set_worklist(const WindowSetCall& c, Seg* segs, const RangePiece* pcs, uint64_t* wl,
-                                      hipStream_t s);
-// launch_window_gather with a stream per window: the tail is found through that
-// stream's last header, and the stream's error word (-91) is the window's status
-hipError_t launch_window_set_gather(const WindowSetCall& c, const RangePiece* pcs, const WindowTail* wt,
-                                    const int64_t* dstat, int64_t* wstat, hipStream_t s);
+// (instantiated for the two sources in lz4_window.hip)
+template <class Source>
+hipError_t launch_window_plan(const Source& src, const WindowCall& c, Seg* segs, RangePiece* pcs,
+                              WindowTail* wt, hipStream_t s);
+// k_range_worklist with every piece's stream taken from the set's record of src.sidx[piece]
+hipError_t launch_window_set_worklist(const WindowSet& src, const WindowCall& c, Seg* segs,
+                                      const RangePiece* pcs, uint64_t* wl, hipStream_t s);
+// status[i] (wstat): c.wbytes, or -71 (bad window), -91 (set: the stream's error
+// word), the code of the highest failing block that holds clip bytes (dstat: the
+// decode's per-block status), or -91 (tail not inside the stream); only windows
+// with c.wbytes are copied.
+template <class Source>
+hipError_t launch_window_gather(const Source& src, const WindowCall& c, const RangePiece* pcs,
+                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s);
+// *result = -91 when *idx_err (nullptr: no index was rebuilt by the call) is set,
+// else -71 when a window was bad, else the status of the highest-numbered
+// failing window, else K * wbytes.
+hipError_t launch_window_reduce(const int64_t* wstat, const WindowTail* wt, int K, const int64_t* idx_err,
+                                int64_t total, int64_t* result, hipStream_t s);
 
 // ---- the reference's internal transpose steps (internals.hip) -------------
 // out[(j * lda + i) * es + t] = in[(i * ldb + j) * es + t]  (bshuf_trans_elem)

@@ -40,10 +40,9 @@ __device__ __forceinline__ void wg_copy(const uint8_t* src, uint8_t* dst, int64_
 }
 
 // One workgroup per piece.  Edge: the clip of the staging block, when the
-// block decoded.  Tail span: from the stream's verbatim tail, which starts
-// where the last record ends (at 0 in a stream without blocks); as in the
-// whole decode, a tail that is not inside the stream is -91 and nothing is
-// copied.
+// block decoded.  Tail span: from the stream's verbatim tail (tail_start,
+// range_worklist.h); a tail that is not inside the stream is -91 and nothing
+// is copied.
 __global__ __launch_bounds__(256) void k_range_edges(RangeStream st, const RangePiece* __restrict__ pcs,
                                                      int64_t* __restrict__ res) {
     const int p = blockIdx.x;
@@ -53,15 +52,8 @@ __global__ __launch_bounds__(256) void k_range_edges(RangeStream st, const Range
     if (pc.kind == kPieceEdge) {
         if (res[p] < 0) return;
     } else {
-        const uint64_t N = (uint64_t)st.in_nbytes;
-        uint64_t ts = 0;
-        bool ok = true;
-        if (st.nb > 0) {
-            const uint64_t h = st.offs[st.nb - 1];
-            ok = h <= N && N - h >= 4;
-            if (ok) ts = h + 4 + be32_at(st.in + h);
-        }
-        ok = ok && ts <= N && N - ts >= (uint64_t)st.tail;
+        uint64_t ts;
+        const bool ok = tail_start(st, ts);
         if (threadIdx.x == 0) res[p] = ok ? pc.n : -91;
         if (!ok) return;
         src = st.in + ts + pc.lo;

@@ -1,7 +1,8 @@
 // range_worklist.h -- the work list of one decode piece, shared by the range
 // and window decodes of one stream (k_range_worklist, lz4_range.hip) and the
-// window decode over a set of streams (k_window_set_worklist,
-// lz4_window_set.hip), whose pieces each name a stream of their own.
+// window decode over a set of streams (k_window_set_worklist, lz4_window.hip),
+// whose pieces each name a stream of their own; and where a stream's verbatim
+// tail starts, for the kernels that copy from it.
 #pragma once
 
 #include "launch.h"
@@ -13,6 +14,20 @@ constexpr uint64_t kNoOffset = ~0ull;  // clamp_span's sentinel: -1001 without a
 __device__ __forceinline__ uint32_t be32_at(const uint8_t* p) {
     const gbl8c* q = (const gbl8c*)p;
     return ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
+}
+
+// Where the verbatim tail of st starts: where the last block's header says its
+// record ends (at 0 in a stream without blocks).  False when the header or the
+// tail is not inside the stream (-91, as in the whole decode).
+__device__ __forceinline__ bool tail_start(const RangeStream& st, uint64_t& ts) {
+    const uint64_t N = (uint64_t)st.in_nbytes;
+    ts = 0;
+    if (st.nb > 0) {
+        const uint64_t h = st.offs[st.nb - 1];
+        if (h > N || N - h < 4) return false;
+        ts = h + 4 + be32_at(st.in + h);
+    }
+    return ts <= N && N - ts >= (uint64_t)st.tail;
 }
 
 // Workgroups (blockIdx.y = 0 .. gridDim.y) share decode piece pc's blocks (a

@@ -1,7 +1,6 @@
 // window_copy.h -- the copy of one window out of its staging area and its
-// stream's verbatim tail, shared by the window decode of one stream
-// (k_window_gather, lz4_window.hip) and of a set of streams
-// (k_window_set_gather, lz4_window_set.hip).
+// stream's verbatim tail, by the window decode of one stream and of a set of
+// streams (k_window_gather, lz4_window.hip).
 #pragma once
 
 #include "launch.h"
@@ -63,8 +62,8 @@ __device__ __forceinline__ void span_copy(const uint8_t* src, uint8_t* dst, int6
 // else the code of the highest failing block among those that hold clip bytes
 // (res: the Seg's result says whether any of its Mw blocks failed; bst: the
 // per-block status of the window's Mw work blocks); else -91 when the window
-// reaches the verbatim tail and that tail is not inside the stream (the rule
-// of k_range_edges); else its byte count wbytes, and only then is it copied.
+// reaches the verbatim tail and that tail is not inside the stream
+// (tail_start); else its byte count wbytes, and only then is it copied.
 __device__ __forceinline__ void window_gather_one(const RangeStream& st, int64_t err, const WindowTail& w,
                                                   const RangePiece* __restrict__ pcs, int i, int64_t res,
                                                   const int64_t* __restrict__ bst, int64_t wbytes,
@@ -81,16 +80,8 @@ __device__ __forceinline__ void window_gather_one(const RangeStream& st, int64_t
                 if (bst[j] < 0) code = bst[j];
         }
         if (code == 0 && w.n > 0) {
-            const uint64_t N = (uint64_t)st.in_nbytes;
-            uint64_t ts = 0;
-            bool ok = true;
-            if (st.nb > 0) {
-                const uint64_t h = st.offs[st.nb - 1];
-                ok = h <= N && N - h >= 4;
-                if (ok) ts = h + 4 + be32_at(st.in + h);
-            }
-            ok = ok && ts <= N && N - ts >= (uint64_t)st.tail;
-            if (ok)
+            uint64_t ts;
+            if (tail_start(st, ts))
                 tsrc = st.in + ts + w.lo;
             else
                 code = -91;

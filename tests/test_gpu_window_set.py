@@ -220,6 +220,49 @@ def test_one_stream_set_is_the_window_decode(bs, torch, make):
                                                               stat1.cpu().tolist()).tobytes()
 
 
+def test_one_stream_and_set_calls_agree(bs, torch, make):
+    """The two entry points run one window decode: the same shuffled starts --
+    every valid one, one in front of the first and one behind the last -- go to
+    the call over the stream and, with ids all zero, to the call over a set of
+    that one stream.  Output bytes (0xA5-filled, with guards), per-window
+    statuses and the result word are compared with each other, not with an
+    expectation; index supplied to both, then rebuilt by both."""
+    b = 64
+    size = 3 * b + 40 + 5      # three full blocks, a partial one, a tail
+    st = make(2, b, size)
+    S = Set(bs, torch, [st])
+    for window in (1, 65, size):
+        wb = window * 2
+        starts = list(range(-1, size - window + 2))
+        K = len(starts)
+        order = np.random.default_rng(window).permutation(K)
+        t = torch.tensor([starts[k] for k in order], dtype=torch.int64, device="cuda")
+        ids = torch.zeros(K, dtype=torch.int64, device="cuda")
+        for supplied in (True, False):
+            got = []
+            for over_set in (False, True):
+                whole = torch.full((GUARD + K * wb + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+                out = whole[GUARD:GUARD + K * wb]
+                status = torch.full((K,), 12345, dtype=torch.int64, device="cuda")
+                if over_set:
+                    _, res = bs.decompress_lz4_windows_set_dev(S.sset(supplied), torch.uint8, ids, t, window,
+                                                               out=out, status=status, elem_size=2, sync=False)
+                else:
+                    _, res = bs.decompress_lz4_windows_dev(st.buf, size, torch.uint8, t, window, b, out=out,
+                                                           status=status, elem_size=2, sync=False,
+                                                           offsets=st.offs if supplied else None)
+                torch.cuda.synchronize()
+                got.append((whole.cpu().numpy().tobytes(), status.cpu().tolist(), int(res.item())))
+            one, over = got
+            key = (window, supplied)
+            assert one[1] == over[1], key
+            assert one[2] == over[2] == -71, key
+            assert one[0] == over[0], key
+            # and they did something: two refused windows, the others written
+            assert sorted(one[1])[:3] == [-71, -71, wb] and one[1].count(wb) == K - 2, key
+            assert one[0][:GUARD] == one[0][-GUARD:] == b"\xa5" * GUARD, key
+
+
 def test_out_of_range_ids_and_starts(bs, torch, make):
     b = 64
     S = Set(bs, torch, [make(2, b, n) for n in (3 * b + 40 + 5, 6 * b + 7, 5 * b)])

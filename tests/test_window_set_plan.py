@@ -1,6 +1,6 @@
 """The plan of the window decode over a set of streams
 (bitshuffle_amd/csrc/window_plan.h, window_set_plan, via libbshuf_hostcheck.so --
-the function k_window_set_plan runs per window on the device) and the host side
+the function k_window_plan runs per window of a set on the device) and the host side
 of bshuf_lz4_stream_set_dev and bshuf_decompress_lz4_windows_set_dev.
 
 The plan, for every stream size up to four blocks, every forced block count Mw
