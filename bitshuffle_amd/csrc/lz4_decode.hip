@@ -355,29 +355,27 @@ __global__ __launch_bounds__(64) void k_idx_walk(IdxArgs x, int64_t nchunks_tota
     }
     const int64_t ce = min((L.s + 1) * CH, Cb);
     int64_t p = chunk_entry(L.in, exits + L.c0, L.s, CH, Cb, maxlen);
-    if (p == kDead) {
-        atomicMax((unsigned long long*)L.err, 1ull);
-        return;
-    }
     uint64_t k = mode ? base[c] - base[L.c0] : 0;  // block index inside the stream
     uint64_t n = 0;
-    while (p < ce) {
-        if (p + 4 > Cb) {
-            atomicMax((unsigned long long*)L.err, 1ull);
-            return;
-        }
-        const uint32_t len = be32_global(L.in + p);
+    // a broken link ends the walk; the count so far is still stored: cnt[c]
+    // is scanned whatever happened here, and a word left as the workspace held
+    // it would put the later chunks' k anywhere
+    bool broken = p == kDead;
+    while (!broken && p < ce) {
+        uint32_t len = 0;
+        if (p + 4 <= Cb) len = be32_global(L.in + p);
         if (len == 0 || len > maxlen || p + 4 + (int64_t)len > Cb) {
-            atomicMax((unsigned long long*)L.err, 1ull);
-            return;
+            broken = true;
+            break;
         }
         if (mode) {
-            if ((int64_t)k < L.nb) offs[L.first + k] = (uint64_t)p;
+            if (k < (uint64_t)L.nb) offs[L.first + k] = (uint64_t)p;
             k++;
         }
         n++;
         p += 4 + len;
     }
+    if (broken) atomicMax((unsigned long long*)L.err, 1ull);
     if (!mode) cnt[c] = n;
 }
 
@@ -1860,6 +1858,10 @@ hipError_t decode_impl(DecArgs& a, int64_t nb, bool aligned, hipStream_t s) {
     // its own, when that still fits the CU's 160 KiB (blocks of some 54 KiB and
     // more with the record in a buffer of its own, the largest 168 bytes of
     // block sizes in place: byte stores instead of a launch the runtime refuses)
+    // E = 1 comes here with an output that is 8- but not 16-byte aligned: byte
+    // stores too, the staged paths' 32-bit reciprocal of E has no value for 1
+    // (2^32 wraps to 0, and every item but the first took group 0)
+    if (ek == 0 && L.E == 1) a.stage_off = 0;
     if (ek == 0 && a.stage_off && (int64_t)L.bs * L.E <= 8192) {
         a.stage_off = -1;
     } else if (ek == 0 && a.stage_off && lds + (size_t)a.cap <= (size_t)160 * 1024) {

@@ -2990,8 +2990,10 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
         // table's LDS as staging (every block of up to ~16 KiB)
         const bool desc = !wide && 4 + lz4_bound((int)nmax) + 15 <= kTableBytes;
         const int32_t desc_off = (int32_t)(((nmax + 15) & ~15) + kDataPad);
+        // (E = 1 from a source that is 8- but not 16-byte aligned is not staged:
+        // the staged transpose's 32-bit reciprocal of E has no value for 1)
         EncArgs a{in, b.scratch, b.foot, b.slot, L, desc ? 1 : 0, desc_off, nullptr, nullptr,
-                  ((uintptr_t)in & 7) == 0 ? 1 : 0};
+                  ((uintptr_t)in & 7) == 0 && L.E != 1 ? 1 : 0};
         const size_t lds = kTableBytes + (size_t)desc_off + (desc ? kDescBytes : 0);
         // the partial block decides its own table type, so a stream whose full
         // blocks need byU32 but partial block byU16 launches twice
@@ -3082,7 +3084,7 @@ hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
                 return hipErrorInvalidValue;  // mixed table types: the caller splits the batch
         const bool desc = !wide && 4 + lz4_bound((int)nmax) + 15 <= kTableBytes;
         const int32_t desc_off = (int32_t)(((nmax + 15) & ~15) + kDataPad);
-        bool raw8 = true;
+        bool raw8 = L.E != 1;  // (as in launch_encode)
         for (int i = 0; i < nsegs; i++) raw8 = raw8 && ((uintptr_t)hsegs[i].in & 7) == 0;
         EncArgs a{nullptr, b.scratch, b.foot, b.slot, L, desc ? 1 : 0, desc_off, segs, blk_seg,
                   raw8 ? 1 : 0};

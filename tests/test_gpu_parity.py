@@ -578,6 +578,39 @@ def test_device_api_unaligned_pointers(bs, oracle, torch):
         assert sh[off_out:off_out + nbytes].cpu().numpy().tobytes() == oracle.bitshuffle(a).tobytes()
 
 
+@pytest.mark.parametrize("E,block", [(1, 0), (1, 64), (1, 16384), (2, 0), (4, 0), (8, 0), (3, 0), (3, 8192)])
+def test_device_api_pointers_8_but_not_16_byte_aligned(bs, oracle, torch, E, block):
+    """Data and output 8 bytes into a 16-byte aligned allocation: the kernels
+    without a register transpose (any element size; 1, 2, 4 and 8 too when a
+    pointer is not 16-byte aligned) stage the bit transpose and store 8-byte
+    words.  E = 1 went wrong there in the encoder and the decoder (the staged
+    paths divide by E with a 32-bit reciprocal, which 1 does not have): wrong
+    bytes, no error.  Blocks of 64 bytes and of 8 KiB take the decoder's
+    register staging, 16 KiB blocks its LDS staging block."""
+    import ctypes
+    nelem = (5 * (block or 4096) + 8 * 37 + 5)
+    raw = oracle.gen_g1((nelem * E + 1) // 2).view(np.uint8)[:nelem * E].copy()
+    a = raw if E == 1 else raw.view(np.dtype("V%d" % E) if E == 3 else {2: np.uint16, 4: np.uint32, 8: np.uint64}[E])
+    want = oracle.compress_lz4(a, block)
+    src = torch.zeros(raw.size + 64, dtype=torch.uint8, device="cuda")
+    assert src.data_ptr() % 16 == 0
+    src[8:8 + raw.size] = torch.from_numpy(raw).cuda()
+    dst = torch.zeros(bs.compress_lz4_bound(nelem, E, block) + 64, dtype=torch.uint8, device="cuda")
+    res = torch.zeros(1, dtype=torch.int64, device="cuda")
+    rc = bs.lib.bshuf_compress_lz4_dev(ctypes.c_void_p(src.data_ptr() + 8), ctypes.c_void_p(dst.data_ptr() + 8),
+                                       nelem, E, block, None, 0, ctypes.c_void_p(res.data_ptr()), None, None)
+    assert rc == 0
+    n = int(res.item())
+    assert dst[8:8 + n].cpu().numpy().tobytes() == want.tobytes()
+    back = torch.zeros(raw.size + 64, dtype=torch.uint8, device="cuda")
+    assert back.data_ptr() % 16 == 0
+    rc = bs.lib.bshuf_decompress_lz4_dev(ctypes.c_void_p(dst.data_ptr() + 8), n, ctypes.c_void_p(back.data_ptr() + 8),
+                                         nelem, E, block, None, 0, ctypes.c_void_p(res.data_ptr()), None, None)
+    assert rc == 0 and int(res.item()) == n
+    assert back[8:8 + raw.size].cpu().numpy().tobytes() == raw.tobytes()
+    assert int(back[:8].max()) == 0 and int(back[8 + raw.size:].max()) == 0
+
+
 # --------------------------------------------------------- pipelined encode
 NO_PIPE = 1 << 20  # bshuf_set_variant bit: encode without segments / side stream
 
