@@ -8,22 +8,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dispatch.h"
 #include "ticket_steal.h"
 
 namespace bshuf {
 
 constexpr int kWave = 64;
 
-// Reference constants (src/bitshuffle_internals.h:33-35, lz4/lz4.c:242-249, 710).
+// Reference constants (src/bitshuffle_internals.h:33-35, lz4/lz4.c:242-249, 710;
+// kMfLimit, kU16TableLimit and lz4_bound: dispatch.h).
 constexpr int kBlockedMult = 8;
 constexpr int kMinMatch = 4;
-constexpr int kMfLimit = 12;
 constexpr int kLastLiterals = 5;
 constexpr int kLz4MinLength = kMfLimit + 1;
-constexpr int kU16TableLimit = 65536 + kMfLimit - 1;  // LZ4_64Klimit
 constexpr uint32_t kMaxDistance = 65535;
-
-__host__ __device__ inline int lz4_bound(int n) { return n + n / 255 + 16; }
 
 // Layout of one framed stream: nfull blocks of bs elements, then one partial
 // block of `last` elements (multiple of 8, may be 0), then `tail` raw bytes.

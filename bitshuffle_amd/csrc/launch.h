@@ -148,8 +148,8 @@ struct Seg {
 // chunks = true chunk_seg[segs[s].chunk0 .. + nchunks) = s.
 hipError_t launch_seg_map(const Seg* segs, int nsegs, uint32_t* map, bool chunks, hipStream_t s);
 
-// Transpose tiles: 256 groups (2048 elements) per 256-thread workgroup.
-constexpr int kTileGroups = 256;
+// Transpose tiles: kTileGroups (dispatch.h) = 256 groups (2048 elements) per
+// 256-thread workgroup.
 
 // bitshuffle / bitunshuffle of all full + partial blocks (tail not included).
 hipError_t launch_transpose(const uint8_t* in, uint8_t* out, const Layout& L, bool forward,
@@ -172,7 +172,6 @@ int64_t encode_slot_bytes(const Layout& L);
 // fast: the blocks' payloads by the fast parse v1 (lz4_fast.hip) instead of the
 // reference's greedy hash parse, when a block is at most kFastMaxBlockBytes;
 // scratch slots, offset scan, compaction and finish are the same.
-constexpr int64_t kFastMaxBlockBytes = 65536;
 hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64_t tail_bytes,
                          const EncodeBufs& b, int64_t* d_result, hipStream_t s, bool fast = false);
 // Batch of independent streams: segs (device) / hsegs (host copy) describe
@@ -183,11 +182,8 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
 hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, const uint32_t* blk_seg,
                                const Layout& L, const EncodeBufs& b, uint64_t* block_offsets,
                                hipStream_t s, bool fast = false);
-// Largest block (bytes) the LDS-resident encoder accepts.
-int64_t max_device_block_bytes();
-// Blocks above these sizes take the global-memory path (lz4_large.hip).
-int64_t max_lds_encode_bytes();
-int64_t max_lds_decode_bytes();
+// (max_device_block_bytes, max_lds_encode_bytes, max_lds_decode_bytes: the
+// sizes above which blocks take the global-memory path, dispatch.h)
 constexpr int64_t kLargeTableWords = 8192;
 // wave-parallel parse of blocks above max_lds_encode_bytes (lz4_encode.hip):
 // shuf holds the bit-transposed blocks (64 bytes of pad behind the last)

@@ -1460,7 +1460,7 @@ void k_lz4_decode(DecArgs a, int64_t nb) {
                 // coalesced 8-byte stores.  No staging buffer: the decoder
                 // keeps 18 resident waves per CU (a staged 8 KiB block needs
                 // 14 LDS granules instead of 7: 9 waves).
-                constexpr int kRegItems = 8192 / 8 / kWave;
+                constexpr int kRegItems = kStageRegBytes / 8 / kWave;
                 const uint32_t magic = (uint32_t)((0x100000000ull + (uint64_t)E - 1) / (uint64_t)E);
                 const int items = P * E;  // 8-byte words of the block, <= 1024
                 uint64_t v[kRegItems];
@@ -1839,8 +1839,6 @@ hipError_t scan_impl(const DecArgs& a, int64_t nb, hipStream_t s) {
 // Scan + decode kernels over nb blocks (one stream, or all streams of a batch).
 hipError_t decode_impl(DecArgs& a, int64_t nb, bool aligned, hipStream_t s) {
     const Layout& L = a.L;
-    // decoded block + record (header, payload, 16-byte alignment slack)
-    const size_t rec = (((size_t)a.maxlen + 4 + 32 + 15) & ~(size_t)15);
     // phase 2 reads each record straight from global memory, so the LDS holds
     // only the decoded block: 18 resident waves per CU instead of 9 (A/B
     // variant 16: the record staged in LDS, as before)
@@ -1850,26 +1848,11 @@ hipError_t decode_impl(DecArgs& a, int64_t nb, bool aligned, hipStream_t s) {
     // default: the record in place at the end of the block's own buffer
     const bool inplace = !grec && tuning_variant() != 64;
     a.ip_end = inplace_end(a.cap);
-    size_t lds = inplace ? (size_t)a.ip_end + 32 : (size_t)a.cap + 16 + (grec ? 0 : rec);
-    const int ek = aligned && (L.E == 1 || L.E == 2 || L.E == 4 || L.E == 8) ? L.E : 0;
-    // any other element size: stage the inverse transpose when every output
-    // is 8-aligned (a.stage_off was set to 1 by the caller as "may") -- through
-    // registers for blocks of <= 8 KiB (stage_off -1), else in an LDS block of
-    // its own, when that still fits the CU's 160 KiB (blocks of some 54 KiB and
-    // more with the record in a buffer of its own, the largest 168 bytes of
-    // block sizes in place: byte stores instead of a launch the runtime refuses)
-    // E = 1 comes here with an output that is 8- but not 16-byte aligned: byte
-    // stores too, the staged paths' 32-bit reciprocal of E has no value for 1
-    // (2^32 wraps to 0, and every item but the first took group 0)
-    if (ek == 0 && L.E == 1) a.stage_off = 0;
-    if (ek == 0 && a.stage_off && (int64_t)L.bs * L.E <= 8192) {
-        a.stage_off = -1;
-    } else if (ek == 0 && a.stage_off && lds + (size_t)a.cap <= (size_t)160 * 1024) {
-        a.stage_off = (int32_t)lds;
-        lds += (size_t)a.cap;
-    } else {
-        a.stage_off = 0;
-    }
+    size_t lds = dec_lds_bytes(a.cap, a.maxlen, inplace, grec);
+    const int ek = pick_ek(L.E, aligned);
+    // any other element size: how the inverse transpose leaves (dec_stage_off,
+    // dispatch.h; a.stage_off was set to 1 by the caller as "may")
+    a.stage_off = dec_stage_off(ek, L.E, (int64_t)L.bs * L.E, a.cap, a.stage_off != 0, lds);
     const void* fn = nullptr;
 #define BSHUF_DEC(ekv, v) reinterpret_cast<const void*>(k_lz4_decode<ekv, v>)
     switch (ek) {
@@ -1975,16 +1958,17 @@ hipError_t launch_decode(const uint8_t* in, int64_t in_nbytes, uint8_t* out, con
     if (e != hipSuccess) return e;
     if (nb > 0) {
         const int64_t nmax = (int64_t)L.bs * L.E;
+        const Align al = align_of((uintptr_t)out);
         DecArgs a{in, in_nbytes, b.offs, out, b.status, b.bad, L, (uint32_t)lz4_bound((int)nmax),
-                  (int32_t)((nmax + 15) & ~15), b.seq, nullptr, nullptr,
-                  ((uintptr_t)out & 7) == 0 ? 1 : 0, 0, 0, nb, dlen, b.tickets};
+                  dec_cap(nmax), b.seq, nullptr, nullptr,
+                  al.a8 ? 1 : 0, 0, 0, nb, dlen, b.tickets};
         if (nmax > max_lds_decode_bytes()) {
             // large blocks: validated by the same scan (a wave per block),
             // executed in global memory
             e = tuning_variant() == 1024 ? scan_impl(a, nb, s) : scan_big_impl(a, nb, s);
             if (e == hipSuccess) e = launch_decode_large(in, in_nbytes, out, L, b, b.shuf, s);
         } else {
-            e = decode_impl(a, nb, ((uintptr_t)out & 15) == 0, s);
+            e = decode_impl(a, nb, al.a16, s);
         }
         if (e != hipSuccess) return e;
     }
@@ -2008,14 +1992,12 @@ hipError_t launch_decode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
     if (e != hipSuccess) return e;
     if (nb > 0) {
         const int64_t nmax = (int64_t)L.bs * L.E;
-        bool aligned = true, al8 = true;
-        for (int i = 0; hsegs && i < nsegs; i++) {  // (no host copy: every output 16-byte aligned)
-            aligned = aligned && ((uintptr_t)hsegs[i].out & 15) == 0;
-            al8 = al8 && ((uintptr_t)hsegs[i].out & 7) == 0;
-        }
+        Align al;
+        for (int i = 0; hsegs && i < nsegs; i++)  // (no host copy: every output 16-byte aligned)
+            al.add((uintptr_t)hsegs[i].out);
         DecArgs a{nullptr, 0, b.offs, nullptr, b.status, b.bad, L, (uint32_t)lz4_bound((int)nmax),
-                  (int32_t)((nmax + 15) & ~15), b.seq, segs, blk_seg, al8 ? 1 : 0, 0, 0, nb, nullptr, b.tickets};
-        e = decode_impl(a, nb, aligned, s);
+                  dec_cap(nmax), b.seq, segs, blk_seg, al.a8 ? 1 : 0, 0, 0, nb, nullptr, b.tickets};
+        e = decode_impl(a, nb, al.a16, s);
         if (e != hipSuccess) return e;
     }
     ProfScope prof("k_decode_finish", s);

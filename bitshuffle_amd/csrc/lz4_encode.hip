@@ -40,7 +40,6 @@ namespace bshuf {
 
 namespace {
 
-constexpr int kTableBytes = 16384;  // byU16: 8192 x u16, byU32: 4096 x u32
 
 // Diagnostic build only (-DBSHUF_DIAG, tools/diag_encode.py): per-phase
 // s_memtime cycle sums and event counters.  The product build compiles these
@@ -147,7 +146,6 @@ struct EmitDiag {};
 #define COUNT(i, v) ((void)0)
 #define DIAG_FLUSH ((void)0)
 #endif
-constexpr int kDataPad = 16;
 
 // Returning LDS atomics as inline asm (no builtin exists for ds_mskor); the
 // asm waits for its own result, so the compiler never reads it early.
@@ -282,8 +280,6 @@ constexpr int kLaneRun = 128;              // emission: longest literal run copi
 constexpr int kFlatLaneRun = 32;           // ... by emit_sequences_flat
 constexpr int kVarEmitFlat = 4194304;      // VAR bit: emit_sequences_flat (the default)
 constexpr int kLaneRunMin = 4;             // ... when the batch has at least this many long runs
-constexpr int kDescMax = 256;              // descriptor slots per block
-constexpr int kDescBytes = 8 * kDescMax;   // LDS behind the block
 
 // Sequence s's descriptor: two dwords in LDS (ip | off << 16, lit | ml << 16,
 // ml = mc + kMinMatch: the match length itself, which the asm re-test loop has
@@ -2111,7 +2107,6 @@ last_literals:
 // EK-specialised paths), land in the still-unused hash-table LDS, and the
 // bit transpose gathers each 8-element group's byte b from there -- the
 // strided byte gathers hit LDS instead of HBM.
-constexpr int kRawBytes = 8192;
 #ifndef BSHUF_EK0_DEFER
 #define BSHUF_EK0_DEFER 1
 #endif
@@ -2186,6 +2181,8 @@ __global__ __launch_bounds__(64) void k_lz4_encode(EncArgs a, int64_t nb) {
     constexpr bool kReadback = (VAR & 128) != 0;
     constexpr int kRegGroups = BlockRegs<EK>::kIters * kWave;
     constexpr int kRegGroups4 = BlockRegs4<EK>::kIters * kWave * 4;
+    static_assert(kRegGroups == enc_reg_groups(EK) && kRegGroups4 == enc_reg_groups4(EK),
+                  "dispatch.h names the prefetch registers' capacities");
     // a block fits the prefetch registers when its groups fit
     auto fits = [&](int m) { return EK != 0 && m / 8 <= kRegGroups; };
     auto fits4 = [&](int m) { return kX4 && EK != 0 && (m / 8) % 4 == 0 && m / 8 <= kRegGroups4; };
@@ -2768,8 +2765,6 @@ hipError_t launch_enc_t(const EncArgs& a, int64_t nb, size_t lds, hipStream_t s)
 
 }  // namespace
 
-int64_t max_device_block_bytes() { return 160 * 1024 - kTableBytes - 64; }
-
 namespace {
 
 // Pipelined encode (launch.h): parse segment i (enc(f_i, f_i+1), the bounds of
@@ -2979,27 +2974,24 @@ hipError_t launch_encode(const uint8_t* in, uint8_t* out, const Layout& L, int64
     hipError_t e = fill_foot_end(b, nb, s);
     if (e != hipSuccess) return e;
     // fast parse v1 covers blocks up to kFastMaxBlockBytes; above, the exact path
-    fast = fast && (int64_t)L.bs * L.E <= kFastMaxBlockBytes;
+    fast = fast && fast_applies((int64_t)L.bs * L.E);
     if (nb > 0 && (int64_t)L.bs * L.E > max_lds_encode_bytes()) {
         e = launch_encode_large(in, L, b, b.shuf, b.tables, s);
         if (e != hipSuccess) return e;
     } else if (nb > 0) {
         const int64_t nmax = (int64_t)L.bs * L.E;
-        const bool wide = nmax >= kU16TableLimit;
-        // sequence descriptors behind the block when the record fits the
-        // table's LDS as staging (every block of up to ~16 KiB)
-        const bool desc = !wide && 4 + lz4_bound((int)nmax) + 15 <= kTableBytes;
-        const int32_t desc_off = (int32_t)(((nmax + 15) & ~15) + kDataPad);
-        // (E = 1 from a source that is 8- but not 16-byte aligned is not staged:
-        // the staged transpose's 32-bit reciprocal of E has no value for 1)
+        // (every path decision: dispatch.h)
+        const bool wide = enc_wide(nmax);
+        const bool desc = enc_desc(nmax);
+        const int32_t desc_off = enc_desc_off(nmax);
+        const Align al = align_of((uintptr_t)in);
         EncArgs a{in, b.scratch, b.foot, b.slot, L, desc ? 1 : 0, desc_off, nullptr, nullptr,
-                  ((uintptr_t)in & 7) == 0 && L.E != 1 ? 1 : 0};
-        const size_t lds = kTableBytes + (size_t)desc_off + (desc ? kDescBytes : 0);
+                  enc_raw8(L.E, al.a8) ? 1 : 0};
+        const size_t lds = enc_lds_bytes(nmax);
         // the partial block decides its own table type, so a stream whose full
         // blocks need byU32 but partial block byU16 launches twice
-        const bool wide_last = L.last && (int64_t)L.last * L.E >= kU16TableLimit;
-        const bool aligned = ((uintptr_t)in & 15) == 0;
-        const int ek = aligned && (L.E == 1 || L.E == 2 || L.E == 4 || L.E == 8) ? L.E : 0;
+        const bool wide_last = L.last && enc_wide((int64_t)L.last * L.E);
+        const int ek = pick_ek(L.E, al.a16);
         auto go = [&](Layout LL, bool w, int64_t count, int64_t first, int set, hipStream_t s) -> hipError_t {
             EncArgs aa = a;
             aa.L = LL;
@@ -3075,23 +3067,21 @@ hipError_t launch_encode_batch(const Seg* segs, const Seg* hsegs, int nsegs, con
     const int64_t nb = L.nfull;  // total blocks of the batch
     hipError_t e = fill_foot_end(b, nb, s);
     if (e != hipSuccess) return e;
-    fast = fast && (int64_t)L.bs * L.E <= kFastMaxBlockBytes;
+    fast = fast && fast_applies((int64_t)L.bs * L.E);
     if (nb > 0) {
         const int64_t nmax = (int64_t)L.bs * L.E;
-        const bool wide = nmax >= kU16TableLimit;
+        const bool wide = enc_wide(nmax);
         for (int i = 0; i < nsegs; i++)
-            if (hsegs[i].last && ((int64_t)hsegs[i].last * L.E >= kU16TableLimit) != wide)
+            if (hsegs[i].last && enc_wide((int64_t)hsegs[i].last * L.E) != wide)
                 return hipErrorInvalidValue;  // mixed table types: the caller splits the batch
-        const bool desc = !wide && 4 + lz4_bound((int)nmax) + 15 <= kTableBytes;
-        const int32_t desc_off = (int32_t)(((nmax + 15) & ~15) + kDataPad);
-        bool raw8 = L.E != 1;  // (as in launch_encode)
-        for (int i = 0; i < nsegs; i++) raw8 = raw8 && ((uintptr_t)hsegs[i].in & 7) == 0;
+        const bool desc = enc_desc(nmax);
+        const int32_t desc_off = enc_desc_off(nmax);
+        Align al;  // (over all streams; as in launch_encode)
+        for (int i = 0; i < nsegs; i++) al.add((uintptr_t)hsegs[i].in);
         EncArgs a{nullptr, b.scratch, b.foot, b.slot, L, desc ? 1 : 0, desc_off, segs, blk_seg,
-                  raw8 ? 1 : 0};
-        const size_t lds = kTableBytes + (size_t)desc_off + (desc ? kDescBytes : 0);
-        bool aligned = true;
-        for (int i = 0; i < nsegs; i++) aligned = aligned && ((uintptr_t)hsegs[i].in & 15) == 0;
-        const int ek = aligned && (L.E == 1 || L.E == 2 || L.E == 4 || L.E == 8) ? L.E : 0;
+                  enc_raw8(L.E, al.a8) ? 1 : 0};
+        const size_t lds = enc_lds_bytes(nmax);
+        const int ek = pick_ek(L.E, al.a16);
         // blocks [f0, f1) of the batch: the segment table is indexed globally
         // (blk0), scratch slots and sizes relative to f0
         auto go = [&](int64_t f0, int64_t f1, int set, hipStream_t s) -> hipError_t {

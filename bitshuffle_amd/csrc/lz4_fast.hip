@@ -146,7 +146,7 @@ __device__ __forceinline__ void put_literals(gbl8* o, int& op, const lds8* D, in
 // w in lane w % 64, register w / 64), reads below the block fall into the
 // bitmaps' tail (their bits are masked), and a block the register transpose
 // does not take (a partial last block) is transposed straight from HBM.
-constexpr int kSregWords = 4 * kWave;
+static_assert(kSregWords == 4 * kWave, "dispatch.h: the match-start bitmap's four registers");
 template <int EK, bool SREG>
 __global__ __launch_bounds__(64) void k_lz4_encode_fast(EncArgs a, int64_t nb, int nw_max) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -180,6 +180,7 @@ __global__ __launch_bounds__(64) void k_lz4_encode_fast(EncArgs a, int64_t nb, i
         bool done = false;
         if constexpr (EK != 0) {
             constexpr int kRegGroups4 = BlockRegs4<EK>::kIters * kWave * 4;
+            static_assert(kRegGroups4 == enc_reg_groups4(EK), "dispatch.h names the registers' capacity");
             if (P % 4 == 0 && P <= kRegGroups4) {
                 BlockRegs4<EK> R4;
                 issue_block_loads4<EK>(R4, src, P, lane);
@@ -373,7 +374,7 @@ __global__ __launch_bounds__(64) void k_lz4_encode_fast(EncArgs a, int64_t nb, i
 template <int EK, bool SREG>
 hipError_t launch_fast_t(const EncArgs& a, int64_t nb, hipStream_t s) {
     const int64_t nmax = (int64_t)a.L.bs * a.L.E;
-    if (nmax > kFastMaxBlockBytes) return hipErrorInvalidValue;
+    if (!fast_applies(nmax)) return hipErrorInvalidValue;
     const int nw_max = (int)((nmax + 31) >> 5);
     // (E = 8 stays in the 8-slot layout: its SREG instance compiled to 170
     // VGPRs = 2 waves per SIMD = 8 blocks per CU by the compiler's report, below
@@ -381,8 +382,7 @@ hipError_t launch_fast_t(const EncArgs& a, int64_t nb, hipStream_t s) {
     // read from the report, not timed)
     if constexpr (EK != 0 && EK != 8 && !SREG) {
         // whole words, the block 16-aligned behind the bitmaps
-        if (nmax % 32 == 0 && nw_max % 4 == 0 && nw_max <= kSregWords)
-            return launch_fast_t<EK, true>(a, nb, s);
+        if (fast_sreg(EK, nmax)) return launch_fast_t<EK, true>(a, nb, s);
     }
     // SREG: 7 bitmap slots + block; else front pad + block (whole words) + back
     // pad + 8 bitmap slots

@@ -233,19 +233,6 @@ __global__ __launch_bounds__(64) void k_lz4_exec_seq(const uint8_t* __restrict__
 
 }  // namespace
 
-int64_t max_lds_encode_bytes() { return max_device_block_bytes(); }
-
-int64_t max_lds_decode_bytes() {
-    // decoded block + 16 + record (bound + header + 32 slack, 16-aligned) in 160 KiB
-    int64_t n = 160 * 1024;
-    while (n > 0) {
-        const int64_t rec = (lz4_bound((int)n) + 4 + 32 + 15) & ~(int64_t)15;
-        if (((n + 15) & ~(int64_t)15) + 16 + rec <= 160 * 1024) break;
-        n -= 8;
-    }
-    return n;
-}
-
 hipError_t launch_encode_large(const uint8_t* in, const Layout& L, const EncodeBufs& b,
                                uint8_t* shuf, uint32_t* tables, hipStream_t s) {
     const int64_t nb = L.nblocks();

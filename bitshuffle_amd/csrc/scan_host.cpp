@@ -1,10 +1,12 @@
 // Host build of the decoder's scan state machine (lz4_scan.h), of the
 // ticket-stealing arithmetic (ticket_steal.h), of the pipelined encode's
 // segment bounds (pipe_segments.h), of the range decode's piece plan
-// (range_plan.h) and of the window decode's plan (window_plan.h) for the CPU
-// test suite.  Not part of the product library.
+// (range_plan.h), of the window decode's plan (window_plan.h) and of the
+// launchers' path decisions (dispatch.h) for the CPU test suite.  Not part of
+// the product library.
 #include <stdint.h>
 
+#include "dispatch.h"
 #include "inplace.h"
 #include "lz4_scan.h"
 #include "pipe_segments.h"
@@ -132,3 +134,91 @@ extern "C" void bshuf_hostcheck_window_set_plan(int64_t count, const int64_t* si
         for (int j = 0; j < 12; j++) out[12 * i + j] = v[j];
     }
 }
+
+// dispatch.h as the launchers use it.  The constants, out[14]: kTableBytes,
+// kRawBytes, kStageRegBytes, kFastMaxBlockBytes, kU16TableLimit,
+// max_device_block_bytes, max_lds_encode_bytes, max_lds_decode_bytes, kDataPad,
+// kDescBytes, kLdsBytes, kTileGroups, kSregWords, kInPlaceMargin.
+extern "C" void bshuf_hostcheck_dispatch_consts(int64_t* out) {
+    const int64_t v[14] = {bshuf::kTableBytes,
+                           bshuf::kRawBytes,
+                           bshuf::kStageRegBytes,
+                           bshuf::kFastMaxBlockBytes,
+                           bshuf::kU16TableLimit,
+                           bshuf::max_device_block_bytes(),
+                           bshuf::max_lds_encode_bytes(),
+                           bshuf::max_lds_decode_bytes(),
+                           bshuf::kDataPad,
+                           bshuf::kDescBytes,
+                           bshuf::kLdsBytes,
+                           bshuf::kTileGroups,
+                           bshuf::kSregWords,
+                           bshuf::kInPlaceMargin};
+    for (int i = 0; i < 14; i++) out[i] = v[i];
+}
+// groups the encoders' prefetch registers hold (four: the 4-groups-per-lane form)
+extern "C" int bshuf_hostcheck_dispatch_reg_groups(int ek, int four) {
+    return four ? bshuf::enc_reg_groups4(ek) : bshuf::enc_reg_groups(ek);
+}
+// launch_encode (n = 1) / launch_encode_batch over sources at these addresses
+// (only their low bits matter), blocks of block_bytes and a partial block of
+// last_bytes (0: none).  out[10]: ek, raw8, desc, wide, wide_last, large,
+// LDS bytes, desc_off, fast applies, fast's SREG layout.
+extern "C" void bshuf_hostcheck_dispatch_encode(int E, int64_t block_bytes, int64_t last_bytes,
+                                                const int64_t* addrs, int n, int64_t* out) {
+    bshuf::Align al;
+    for (int i = 0; i < n; i++) al.add((uintptr_t)addrs[i]);
+    const int ek = bshuf::pick_ek(E, al.a16);
+    const int64_t v[10] = {ek,
+                           bshuf::enc_raw8(E, al.a8),
+                           bshuf::enc_desc(block_bytes),
+                           bshuf::enc_wide(block_bytes),
+                           last_bytes && bshuf::enc_wide(last_bytes),
+                           block_bytes > bshuf::max_lds_encode_bytes(),
+                           (int64_t)bshuf::enc_lds_bytes(block_bytes),
+                           bshuf::enc_desc_off(block_bytes),
+                           bshuf::fast_applies(block_bytes),
+                           bshuf::fast_sreg(ek, block_bytes)};
+    for (int i = 0; i < 10; i++) out[i] = v[i];
+}
+// launch_decode (n = 1) / launch_decode_batch with outputs at these addresses.
+// out[5]: large, ek, stage_off (0 byte stores, -1 registers, else the LDS
+// offset), LDS bytes of a workgroup, cap.
+extern "C" void bshuf_hostcheck_dispatch_decode(int E, int64_t block_bytes, const int64_t* addrs, int n,
+                                                int inplace, int grec, int64_t* out) {
+    bshuf::Align al;
+    for (int i = 0; i < n; i++) al.add((uintptr_t)addrs[i]);
+    const int ek = bshuf::pick_ek(E, al.a16);
+    const int32_t cap = bshuf::dec_cap(block_bytes);
+    size_t lds = bshuf::dec_lds_bytes(cap, (uint32_t)bshuf::lz4_bound((int)block_bytes), inplace != 0, grec != 0);
+    const int32_t so = bshuf::dec_stage_off(ek, E, block_bytes, cap, al.a8, lds);
+    const int64_t v[5] = {block_bytes > bshuf::max_lds_decode_bytes(), ek, so, (int64_t)lds, cap};
+    for (int i = 0; i < 5; i++) out[i] = v[i];
+}
+// ... both for every residue 0..15 of one pointer (out: 16 x 15 words, the
+// encoder's 10 then the decoder's 5) ...
+extern "C" void bshuf_hostcheck_dispatch_residues(int E, int64_t block_bytes, int64_t last_bytes, int inplace,
+                                                  int grec, int64_t* out) {
+    for (int r = 0; r < 16; r++) {
+        const int64_t a = 0x10000 + r;
+        bshuf_hostcheck_dispatch_encode(E, block_bytes, last_bytes, &a, 1, out + 15 * r);
+        bshuf_hostcheck_dispatch_decode(E, block_bytes, &a, 1, inplace, grec, out + 15 * r + 10);
+    }
+}
+// ... and for every pair of residues of a batch of two (out: 256 x 15 words)
+extern "C" void bshuf_hostcheck_dispatch_pairs(int E, int64_t block_bytes, int64_t* out) {
+    for (int r = 0; r < 256; r++) {
+        const int64_t a[2] = {0x10000 + r / 16, 0x20000 + r % 16};
+        bshuf_hostcheck_dispatch_encode(E, block_bytes, 0, a, 2, out + 15 * r);
+        bshuf_hostcheck_dispatch_decode(E, block_bytes, a, 2, 1, 0, out + 15 * r + 10);
+    }
+}
+// launch_transpose: the tile kernels (1) or the byte-granular one (0) ...
+extern "C" int bshuf_hostcheck_dispatch_transpose(int E, int64_t in_addr, int64_t out_addr) {
+    bshuf::Align al;
+    al.add((uintptr_t)in_addr);
+    al.add((uintptr_t)out_addr);
+    return bshuf::transpose_fast(E, al.a16) ? 1 : 0;
+}
+// ... and a tile of ng groups of a block of P: 16-byte rows (1) or bytes (0)
+extern "C" int bshuf_hostcheck_dispatch_rows16(int P, int ng) { return bshuf::transpose_rows16(P, ng) ? 1 : 0; }

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_bitshuffle_fast(const uint8_t* __restri
     }
     __syncthreads();
     const int rows = 8 * EK;
-    if ((P & 15) == 0 && (tm.ng & 15) == 0) {
+    if ((P & 15) == 0 && (tm.ng & 15) == 0) {  // (transpose_rows16, dispatch.h)
         const int chunks = tm.ng >> 4;
         for (int i = t; i < rows * chunks; i += 256) {
             const int r = i / chunks, c = i - r * chunks;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void k_bitunshuffle_fast(const uint8_t* __rest
     const uint8_t* src = in + boff;
     uint8_t* dst = out + boff;
     const int rows = 8 * EK;
-    if ((P & 15) == 0 && (tm.ng & 15) == 0) {
+    if ((P & 15) == 0 && (tm.ng & 15) == 0) {  // (transpose_rows16, dispatch.h)
         const int chunks = tm.ng >> 4;
         for (int i = t; i < rows * chunks; i += 256) {
             const int r = i / chunks, c = i - r * chunks;
@@ -163,8 +163,10 @@ hipError_t launch_transpose(const uint8_t* in, uint8_t* out, const Layout& L, bo
     if (tiles == 0) return hipSuccess;
     const dim3 grid((unsigned)tiles), block(256);
     ProfScope prof(forward ? "k_bitshuffle" : "k_bitunshuffle", s);
-    const bool aligned = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-    if (aligned && (L.E == 1 || L.E == 2 || L.E == 4 || L.E == 8)) {
+    Align al;
+    al.add((uintptr_t)in);
+    al.add((uintptr_t)out);
+    if (transpose_fast(L.E, al.a16)) {
 #define BSHUF_T(EK)                                                                        \
     case EK:                                                                               \
         if (forward)                                                                       \
