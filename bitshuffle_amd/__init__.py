@@ -31,6 +31,14 @@ starts[i], both DEVICE tensors; the set is built once
     lz4_stream_set_dev(bufs, sizes, elem_size, block_size=0, offsets=None, ...) -> StreamSet
     decompress_lz4_windows_set_dev(sset, dtype, ids, starts, window, ...) -> (K, window)
     decompress_lz4_windows_set_workspace(sset, nwindows, window, ...)
+Tile decode (device): K crops of rows x cols elements at row pitch `pitch`, row r
+of tile i being elements [starts[i] + r * pitch, ... + cols) of one stream or of
+stream ids[i] of a set; rows that share blocks are decoded together, a tile with
+a failing block is not written at all
+    decompress_lz4_tiles_dev(buf, size, dtype, starts, rows, cols, pitch, ...) -> (K, rows, cols)
+    decompress_lz4_tiles_workspace(in_nbytes, size, elem_size, ntiles, rows, cols, pitch, ...)
+    decompress_lz4_tiles_set_dev(sset, dtype, ids, starts, rows, cols, pitch, ...) -> (K, rows, cols)
+    decompress_lz4_tiles_set_workspace(sset, ntiles, rows, cols, pitch, ...)
 """
 from ._lib import (  # noqa: F401
     LIB_PATH,
@@ -59,6 +67,10 @@ from .api import (  # noqa: F401
     decompress_lz4_range_dev,
     decompress_lz4_ranges_dev,
     decompress_lz4_ranges_workspace,
+    decompress_lz4_tiles_dev,
+    decompress_lz4_tiles_set_dev,
+    decompress_lz4_tiles_set_workspace,
+    decompress_lz4_tiles_workspace,
     decompress_lz4_windows_dev,
     decompress_lz4_windows_set_dev,
     decompress_lz4_windows_set_workspace,
@@ -97,5 +109,9 @@ __all__ = [
     "lz4_stream_set_dev",
     "decompress_lz4_windows_set_dev",
     "decompress_lz4_windows_set_workspace",
+    "decompress_lz4_tiles_dev",
+    "decompress_lz4_tiles_workspace",
+    "decompress_lz4_tiles_set_dev",
+    "decompress_lz4_tiles_set_workspace",
     "FAST_PARSE_VERSION",
 ]

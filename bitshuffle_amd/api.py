@@ -501,6 +501,127 @@ def decompress_lz4_windows_set_dev(sset, dtype, ids, starts, window, out=None, w
                         workspace, result, status, sync, elem_size, holds=sset.elem_size)
 
 
+def _tiles_dev(call, device, whose, index, dtype, rows, cols, pitch, out, workspace, result, status, sync,
+               elem_size, holds=None):
+    """What the tile decodes of one stream and of a set share, as _windows_dev
+    for the window decodes.  `index`: (name, tensor) pairs, the device tensors
+    with one entry per tile each.  call(es, K, rows, cols, pitch, out, ws,
+    ws_bytes, result, status) makes the library call with these arguments of its
+    own among the others and returns its code."""
+    torch = _torch()
+    for name, t in index:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+                and t.device == device):
+            raise ValueError("%s must be a contiguous int64 tensor on the %s device" % (name, whose))
+    counts = [t.numel() for _, t in index]
+    if len(set(counts)) > 1:
+        raise ValueError("%s need one entry per tile (%s)" % (" and ".join(name for name, _ in index),
+                                                              " and ".join("%d" % n for n in counts)))
+    K, rows, cols, pitch = counts[-1], int(rows), int(cols), int(pitch)
+    for name, v in (("rows", rows), ("cols", cols), ("pitch", pitch)):
+        if v < 0:
+            raise ValueError("%s must be >= 0, not %d" % (name, v))
+    if out is None:
+        if elem_size is None:
+            out = torch.empty((K, rows, cols), dtype=dtype, device=device)
+        else:
+            out = torch.empty((K, rows, cols * int(elem_size)), dtype=torch.uint8, device=device)
+    es = out.element_size() if elem_size is None else int(elem_size)
+    if holds is not None and es != holds:
+        raise ValueError("the set holds %d-byte elements, not %d-byte ones" % (holds, es))
+    if out.numel() * out.element_size() < K * rows * cols * es:
+        raise ValueError("out holds %d bytes, the tiles need %d"
+                         % (out.numel() * out.element_size(), K * rows * cols * es))
+    if status is not None and (status.dtype != torch.int64 or status.numel() < K):
+        raise ValueError("status must be an int64 tensor of %d entries" % K)
+    if result is None:
+        result = torch.empty(1, dtype=torch.int64, device=device)
+    ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+    wsb = workspace.numel() if workspace is not None else 0
+    stp = _dptr(status) if status is not None else None
+    _check(call(es, K, rows, cols, pitch, _dptr(out), ws, wsb, _dptr(result), stp))
+    if not sync:
+        return out, result
+    count = int(result.item())
+    if count < 0:
+        _fail(count)
+    return out
+
+
+def decompress_lz4_tiles_workspace(in_nbytes, size, elem_size, ntiles, rows, cols, pitch, block_size=0,
+                                   device=None):
+    """A workspace for decompress_lz4_tiles_dev of `ntiles` tiles of rows x cols
+    elements at row pitch `pitch` of a stream of `in_nbytes` bytes: its size
+    depends on these numbers only, never on the starts."""
+    torch = _torch()
+    n = int(lib.bshuf_decompress_lz4_tiles_dev_workspace(in_nbytes, size, elem_size, block_size, ntiles, rows,
+                                                         cols, pitch))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device or "cuda")
+
+
+def decompress_lz4_tiles_dev(buf, size, dtype, starts, rows, cols, pitch, block_size=0, out=None,
+                             workspace=None, result=None, status=None, offsets=None, stream=None,
+                             sync=True, elem_size=None):
+    """Tile decode (bshuf_decompress_lz4_tiles_dev): K = starts.numel() tiles of
+    rows x cols elements each of the framed stream in uint8 device tensor `buf`,
+    which encodes `size` elements of `dtype`.  Row r of tile i is elements
+    [starts[i] + r * pitch, ... + cols): for a 2-D array of row length `pitch` a
+    crop with its corner at (y, x) has start y * pitch + x.  `starts` is a
+    contiguous int64 DEVICE tensor of flat element indices, read by the kernels
+    only: nothing here copies it to the host, and a call captured into a graph
+    decodes whatever starts the tensor holds at each replay.  Returns a (K,
+    rows, cols) tensor of `dtype` -- with `elem_size` a uint8 tensor (K, rows,
+    cols * elem_size) -- (sync=True), or (out, result) with result a 1-element
+    int64 device tensor of the byte count / error code (sync=False).  `status`
+    (int64 device tensor, K entries): per tile its byte count, -71 for a start
+    outside [0, size - ((rows - 1) * pitch + cols)], or the code of a failing
+    block that holds one of its elements; a tile with a negative status is left
+    as it was in `out`, all of it.  `offsets`: the stream's block index; without
+    it the index is rebuilt from the whole stream."""
+    def call(es, K, rows, cols, pitch, *ptrs):
+        offp = _dptr(offsets) if offsets is not None else None
+        return lib.bshuf_decompress_lz4_tiles_dev(_dptr(buf), buf.numel(), int(size), es, block_size,
+                                                  _dptr(starts), K, rows, cols, pitch, *ptrs, offp,
+                                                  _stream(stream))
+    return _tiles_dev(call, buf.device, "stream's", [("starts", starts)], dtype, rows, cols, pitch, out,
+                      workspace, result, status, sync, elem_size)
+
+
+def decompress_lz4_tiles_set_workspace(sset, ntiles, rows, cols, pitch, device=None):
+    """A workspace for decompress_lz4_tiles_set_dev of `ntiles` tiles of rows x
+    cols elements at row pitch `pitch` over StreamSet `sset`: its size depends on
+    the set's largest stream, element and block size and these numbers only."""
+    torch = _torch()
+    n = int(lib.bshuf_decompress_lz4_tiles_set_dev_workspace(sset.max_size, sset.elem_size, sset.block_size,
+                                                             ntiles, rows, cols, pitch))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device or sset.device)
+
+
+def decompress_lz4_tiles_set_dev(sset, dtype, ids, starts, rows, cols, pitch, out=None, workspace=None,
+                                 result=None, status=None, stream=None, sync=True, elem_size=None):
+    """Tile decode over a StreamSet (bshuf_decompress_lz4_tiles_set_dev): row r
+    of tile i is elements [starts[i] + r * pitch, ... + cols) of stream ids[i] --
+    a rows x cols crop of frame ids[i] of a stack of images stored one stream
+    each.  `ids` and `starts` are contiguous int64 DEVICE tensors of equal
+    length K, read by the kernels only: nothing here copies them to the host,
+    and a call captured into a graph follows both at every replay.  Returns a
+    (K, rows, cols) tensor of `dtype` -- with `elem_size` a uint8 tensor (K,
+    rows, cols * elem_size) -- (sync=True, which reads only `result`), or (out,
+    result) (sync=False).  `status` (int64 device tensor, K entries): per tile
+    its byte count; -71 for an id outside the set, a start outside [0, size -
+    span] of its stream (span = (rows - 1) * pitch + cols) or a stream with
+    fewer blocks than a group of the tile's rows decodes (that tile's part of
+    `out` is left as it was); -91 for a stream whose rebuilt index failed; or
+    the code of a failing block that holds one of the tile's elements, and then
+    none of the tile is written."""
+    def call(es, K, rows, cols, pitch, *ptrs):
+        return lib.bshuf_decompress_lz4_tiles_set_dev(_dptr(sset.table), sset.count, sset.max_size, es,
+                                                      sset.block_size, _dptr(ids), _dptr(starts), K, rows, cols,
+                                                      pitch, *ptrs, _stream(stream))
+    return _tiles_dev(call, sset.device, "set's", [("ids", ids), ("starts", starts)], dtype, rows, cols, pitch,
+                      out, workspace, result, status, sync, elem_size, holds=sset.elem_size)
+
+
 def block_index_dev(buf, size, elem_size, block_size=0, workspace=None, stream=None):
     """The block index of the framed stream in uint8 device tensor `buf` for
     `size` elements of `elem_size` bytes (bshuf_lz4_block_index_dev, the

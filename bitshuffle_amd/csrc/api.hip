@@ -17,6 +17,7 @@
 #include "launch.h"
 #include "plan.h"
 #include "range_plan.h"
+#include "tile_plan.h"
 #include "window_plan.h"
 
 using namespace bshuf;
@@ -1278,6 +1279,249 @@ int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, si
             const hipError_t e = dev_fill(b.d.idx_err, 0, (size_t)c.K * 8, s);
             if (e != hipSuccess) return e;
             return launch_window_set_worklist(src, c, b.segs, b.pcs, b.d.offs, s);
+        });
+}
+
+// ---------------------------------------------------------------------------
+// rows x cols tiles at device-held flat starts, of one stream or of a set
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// What the host knows of a tile call, over one stream or over a set:
+// everything but the starts (and the stream indices).
+struct TileShapeH {
+    int64_t K = 0, rows = 0, cols = 0, pitch = 0;
+    TileShape t{0, 0, 0};   // rg, G, Mg (tile_plan.h)
+    int64_t seq_words = 0;  // token positions: a private area per group, or (shared_seq) the
+    bool shared_seq = false;  // whole decode's area indexed by stream offset, when that is smaller
+    int64_t pw = 0;         // words of one private area
+    int64_t slot = 0;       // bytes of one staging area
+    bool set = false;       // over a set: a stream index per group, no index rebuild
+    bool empty = false;     // ntiles, rows or cols is 0: nothing to decode
+};
+
+// p, size: of the stream, or (set) of the set's largest stream; as window_shape.
+int64_t tile_shape_host(const Plan& p, size_t size, size_t in_nbytes, size_t ntiles, size_t rows, size_t cols,
+                        size_t pitch, bool set, TileShapeH& w) {
+    const Layout& L = p.L;
+    w.set = set;
+    w.empty = ntiles == 0 || rows == 0 || cols == 0;
+    if (ntiles >= ((uint64_t)1 << 31)) return kErrUnsupported;
+    if ((int64_t)L.bs * L.E > max_lds_decode_bytes()) return kErrUnsupported;
+    w.K = (int64_t)ntiles;
+    if (!w.empty) {
+        if (pitch < cols) return kErrUnsupported;
+        // span = (rows - 1) * pitch + cols <= size, without overflow
+        if (cols > size || (rows > 1 && pitch > (size - cols) / (rows - 1))) return kErrUnsupported;
+        // the output's byte count fits int64
+        const unsigned __int128 total = (unsigned __int128)ntiles * rows * cols * (uint64_t)L.E;
+        if (total >= ((unsigned __int128)1 << 62)) return kErrUnsupported;
+        w.rows = (int64_t)rows;
+        w.cols = (int64_t)cols;
+        w.pitch = (int64_t)pitch;
+        tile_shape(w.rows, w.cols, w.pitch, L.bs, p.nb, w.t);
+        const unsigned __int128 pieces = (unsigned __int128)ntiles * (uint64_t)w.t.G;
+        if (pieces >= ((uint64_t)1 << 31) || pieces * (uint64_t)w.t.Mg >= ((uint64_t)1 << 31)) return kErrUnsupported;
+    }
+    const int64_t maxlen = lz4_bound(L.bs * L.E);
+    const int64_t pieces = w.K * w.t.G;
+    w.pw = w.t.Mg * (4 + maxlen) / 3 + 80;
+    const int64_t shared_words = (int64_t)in_nbytes / 3 + 80;
+    w.shared_seq = !set && shared_words < pieces * w.pw;
+    w.seq_words = w.shared_seq ? shared_words : pieces * w.pw;
+    w.slot = (w.t.Mg * (int64_t)L.bs * L.E + 15) & ~(int64_t)15;
+    return 0;
+}
+
+struct TileBufs {
+    Seg* segs;
+    RangePiece* pcs;
+    TileInfo* ti;
+    uint32_t* blk_seg;
+    DecodeBufs d;    // offs: the work list; idx_err: zeros, one per group
+    int64_t* res;    // one per group: its Seg's result
+    int64_t* tstat;  // one per tile, when the caller passes no d_status
+    uint8_t* slots;  // staging areas
+    DecodeBufs idx;  // one stream: index rebuild of the whole stream (offs: its block index)
+    int32_t* sidx;   // set: per group, its stream
+};
+
+// K * G Seg and RangePiece records, K TileInfo, K * G * Mg work blocks (map,
+// offsets, status), the token positions, K * G staging areas of Mg blocks, and
+// the index rebuild's buffers (one stream) or the groups' stream indices (set).
+size_t tile_ws(const Plan& p, const TileShapeH& w, int64_t blocks_end, TileBufs* b, uint8_t* base) {
+    Carver c{base};
+    TileBufs x{};
+    const size_t K = (size_t)w.K, P = (size_t)(w.K * w.t.G), nwork = P * (size_t)w.t.Mg;
+    x.segs = c.take<Seg>(P * sizeof(Seg));
+    x.pcs = c.take<RangePiece>(P * sizeof(RangePiece));
+    x.ti = c.take<TileInfo>(K * sizeof(TileInfo));
+    x.blk_seg = c.take<uint32_t>(nwork * 4 + 4);
+    x.d.offs = c.take<uint64_t>(nwork * 8 + 8);
+    x.d.status = c.take<int64_t>(nwork * 8 + 8);
+    x.d.seq = c.take<uint32_t>((size_t)w.seq_words * 4);
+    x.d.idx_err = c.take<int64_t>(P * 8 + 8);
+    x.d.bad = c.take<long long>(P * 8 + 8);
+    x.d.tickets = c.take<uint32_t>(kTicketSetBytes);
+    x.res = c.take<int64_t>(P * 8 + 8);
+    x.tstat = c.take<int64_t>(K * 8 + 8);
+    x.slots = c.take<uint8_t>(P * (size_t)w.slot);
+    if (w.set)
+        x.sidx = c.take<int32_t>(P * 4 + 4);
+    else
+        carve_index(c, p, blocks_end, x.idx);
+    if (b) *b = x;
+    return c.off;
+}
+
+// What the two tile entry points share, from the workspace to the result; the
+// two callables as window_decode's, with a group in a window's place.
+extern "C++" template <class MakeSource, class Worklist>
+int64_t tile_decode(const Plan& p, const TileShapeH& w, int64_t blocks_end, size_t need, const int64_t* d_starts,
+                    void* out, void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status, hipStream_t s,
+                    MakeSource make_source, Worklist worklist) {
+    DevBuf own;
+    const int64_t r = get_ws(ws, ws_bytes, need, own, s);
+    if (r) return r;
+    TileBufs b;
+    tile_ws(p, w, blocks_end, &b, (uint8_t*)ws);
+    const int K = (int)w.K, P = (int)(w.K * w.t.G);
+    int64_t* tstat = d_status ? d_status : b.tstat;
+
+    auto src = make_source(b);
+    TileCall c{};
+    c.starts = d_starts;
+    c.out = (uint8_t*)out;
+    c.slots = b.slots;
+    c.res = b.res;
+    c.rows = w.rows;
+    c.cols = w.cols;
+    c.pitch = w.pitch;
+    c.rg = w.t.rg;
+    c.G = w.t.G;
+    c.Mg = w.t.Mg;
+    c.rbytes = w.cols * p.L.E;
+    c.slot = w.slot;
+    c.seq_words = w.shared_seq ? -1 : w.pw;
+    c.bs = p.L.bs;
+    c.E = p.L.E;
+    c.K = K;
+    if (launch_tile_plan(src, c, b.segs, b.pcs, b.ti, s) != hipSuccess) return kErrHip;
+    const int64_t* idx_err = nullptr;
+    if (worklist(src, c, b, idx_err) != hipSuccess) return kErrHip;
+    if (c.Mg > 0) {
+        // every group's staging area is 16-byte aligned: one scan and one decode
+        // launch over all K * G * Mg work blocks, no host copy of the table
+        Layout L = p.L;
+        L.nfull = (int64_t)P * c.Mg;
+        L.last = 0;
+        if (launch_seg_map(b.segs, P, b.blk_seg, false, s) != hipSuccess ||
+            launch_decode_batch(b.segs, nullptr, P, b.blk_seg, L, b.d, s) != hipSuccess)
+            return kErrHip;
+    }
+    if (launch_tile_gather(src, c, b.pcs, b.ti, b.d.status, tstat, s) != hipSuccess ||
+        launch_tile_reduce(tstat, b.ti, K, idx_err, w.K * c.rows * c.rbytes, d_result, s) != hipSuccess)
+        return kErrHip;
+    return 0;
+}
+
+}  // namespace
+
+size_t bshuf_decompress_lz4_tiles_dev_workspace(size_t in_nbytes, size_t size, size_t elem_size,
+                                                size_t block_size, size_t ntiles, size_t rows, size_t cols,
+                                                size_t pitch) {
+    Plan p;
+    TileShapeH w;
+    if (make_plan(size, elem_size, block_size, p) ||
+        tile_shape_host(p, size, in_nbytes, ntiles, rows, cols, pitch, false, w))
+        return 0;
+    const int64_t cb = (int64_t)in_nbytes - p.tail;
+    return tile_ws(p, w, cb > 0 ? cb : 0, nullptr, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_tiles_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                       size_t block_size, const int64_t* d_starts, size_t ntiles, size_t rows,
+                                       size_t cols, size_t pitch, void* out, void* ws, size_t ws_bytes,
+                                       int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
+                                       void* stream) {
+    Plan p;
+    int64_t r = make_plan(size, elem_size, block_size, p);
+    if (r) return r;
+    TileShapeH w;
+    r = tile_shape_host(p, size, in_nbytes, ntiles, rows, cols, pitch, false, w);
+    if (r) return r;
+    int64_t cb = (int64_t)in_nbytes - p.tail;
+    if (cb < 0) cb = 0;
+    const size_t need = tile_ws(p, w, cb, nullptr, nullptr);
+    if (ws && (ws_bytes < need || ((uintptr_t)ws & 255))) return kErrUnsupported;
+    if (!have_device()) return kErrHip;
+    hipStream_t s = (hipStream_t)stream;
+    if (w.empty) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
+    const uint8_t* i8 = (const uint8_t*)in;
+    return tile_decode(
+        p, w, cb, need, d_starts, out, ws, ws_bytes, d_result, d_status, s,
+        // the plan reads the stream's address and size only: the index comes behind it
+        [&](const TileBufs&) { return WindowStream{RangeStream{i8}, (int64_t)size}; },
+        [&](WindowStream& src, const TileCall& c, const TileBufs& b, const int64_t*& idx_err) {
+            hipError_t e = stream_with_index(i8, in_nbytes, cb, p, block_offsets, b.idx, s, src.st, idx_err);
+            if (e != hipSuccess || c.Mg <= 0) return e;
+            const int P = (int)(c.K * c.G);
+            e = dev_fill(b.d.idx_err, 0, (size_t)P * 8, s);
+            if (e != hipSuccess) return e;
+            return launch_range_worklist(src.st, b.segs, b.pcs, P, P, 0, c.Mg, b.d.offs, s);
+        });
+}
+
+size_t bshuf_decompress_lz4_tiles_set_dev_workspace(size_t max_size, size_t elem_size, size_t block_size,
+                                                    size_t ntiles, size_t rows, size_t cols, size_t pitch) {
+    Plan p;
+    TileShapeH w;
+    if (make_plan(max_size, elem_size, block_size, p) ||
+        tile_shape_host(p, max_size, 0, ntiles, rows, cols, pitch, true, w))
+        return 0;
+    return tile_ws(p, w, 0, nullptr, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_tiles_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                           size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                           size_t ntiles, size_t rows, size_t cols, size_t pitch, void* out,
+                                           void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                           void* stream) {
+    Plan p;
+    int64_t r = make_plan(max_size, elem_size, block_size, p);
+    if (r) return r;
+    TileShapeH w;
+    r = tile_shape_host(p, max_size, 0, ntiles, rows, cols, pitch, true, w);
+    if (r) return r;
+    if (count > (size_t)INT32_MAX) return kErrUnsupported;
+    const size_t need = tile_ws(p, w, 0, nullptr, nullptr);
+    if (ws && (ws_bytes < need || ((uintptr_t)ws & 255))) return kErrUnsupported;
+    if (!d_set || ((uintptr_t)d_set & 255)) return kErrUnsupported;
+    if (!have_device()) return kErrHip;
+    hipStream_t s = (hipStream_t)stream;
+    if (w.empty) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
+    return tile_decode(
+        p, w, 0, need, d_starts, out, ws, ws_bytes, d_result, d_status, s,
+        [&](const TileBufs& b) {
+            return WindowSet{(const StreamSetHeader*)d_set,
+                             (const StreamSetRec*)((const uint8_t*)d_set + kStreamSetRecs),
+                             d_ids,
+                             b.sidx,
+                             (int64_t)count,
+                             p.nb};
+        },
+        // (the set's indexes were made by its build: nothing to rebuild)
+        [&](const WindowSet& src, const TileCall& c, const TileBufs& b, const int64_t*&) {
+            if (c.Mg <= 0) return hipSuccess;
+            const int64_t P = (int64_t)c.K * c.G;
+            const hipError_t e = dev_fill(b.d.idx_err, 0, (size_t)P * 8, s);
+            if (e != hipSuccess) return e;
+            // the window decode's work list, a group being its window
+            WindowCall wc{};
+            wc.K = (int32_t)P;
+            wc.Mw = c.Mg;
+            return launch_window_set_worklist(src, wc, b.segs, b.pcs, b.d.offs, s);
         });
 }
 

@@ -384,6 +384,59 @@ hipError_t launch_window_gather(const Source& src, const WindowCall& c, const Ra
 hipError_t launch_window_reduce(const int64_t* wstat, const WindowTail* wt, int K, const int64_t* idx_err,
                                 int64_t total, int64_t* result, hipStream_t s);
 
+// ---- tile decode (lz4_tile.hip) -------------------------------------------
+// K tiles of rows x cols elements at DEVICE-held flat starts, row r of tile i
+// being elements [starts[i] + r * pitch, ... + cols) of one stream
+// (bshuf_decompress_lz4_tiles_dev) or of stream ids[i] of a set
+// (bshuf_decompress_lz4_tiles_set_dev).  The host-known shape (tile_plan.h,
+// tile_shape) cuts every tile into G groups of rg rows; a group is what a
+// window is to the window decode -- Seg i * G + g of Mg consecutive blocks,
+// decoded back to back into staging area i * G + g -- so the work list,
+// launch_seg_map and launch_decode_batch run as they do there over K * G pieces.
+// k_tile_plan writes the tables from the starts (and ids); k_tile_gather settles
+// every tile's status and copies the rows of the good ones out of their groups'
+// areas and the verbatim tail; k_tile_reduce makes the call's result.  The
+// sources are the window decode's.
+struct TileInfo {
+    int64_t start;  // the tile's flat element index
+    int32_t bad;    // refused (-71): start out of range, or (set) no stream that takes the tile
+    int32_t sidx;   // set: the tile's stream (a bad tile: none)
+};
+struct TileCall {
+    const int64_t* starts;  // device, K element indices
+    uint8_t* out;           // row r of tile i at out + (i * rows + r) * rbytes
+    uint8_t* slots;         // K * G staging areas of `slot` bytes (16-aligned)
+    int64_t* res;           // per group: its Seg's result
+    int64_t rows, cols, pitch;
+    int64_t rg, G, Mg;      // tile_shape
+    int64_t rbytes, slot;   // bytes of a row, of a staging area
+    int64_t seq_words;      // per group, of its own token-position area; -1: the shared area
+    int32_t bs, E;
+    int32_t K, pad_;
+};
+// Seg, RangePiece and (set) src.sidx entries i * G + g, TileInfo i.  A bad tile
+// of a set decodes blocks [0, Mg) of the set's stream `ref`; with a mismatched
+// header no tile has a stream (sidx -1: sentinel offsets), as for windows.
+template <class Source>
+hipError_t launch_tile_plan(const Source& src, const TileCall& c, Seg* segs, RangePiece* pcs, TileInfo* ti,
+                            hipStream_t s);
+// status[i] (tstat): rows * rbytes, or -71 (bad tile), -91 (set: the stream's
+// error word), the code of the highest failing block -- in stream order -- among
+// those that hold an element of the tile (dstat: the decode's per-block
+// status), or -91 (a row reaches a verbatim tail that is not inside the stream);
+// only tiles with rows * rbytes are copied, the others not at all.
+template <class Source>
+hipError_t launch_tile_gather(const Source& src, const TileCall& c, const RangePiece* pcs, const TileInfo* ti,
+                              const int64_t* dstat, int64_t* tstat, hipStream_t s);
+// A/B of the gather's lanes per row (bshuf_set_variant; values of their own,
+// which no other kernel reads): 16, 64 or 256 whatever the row's bytes.
+constexpr int kTileLanes16 = 1 << 22;
+constexpr int kTileLanes64 = 1 << 23;
+constexpr int kTileLanes256 = kTileLanes16 | kTileLanes64;
+// launch_window_reduce's rule over tiles.
+hipError_t launch_tile_reduce(const int64_t* tstat, const TileInfo* ti, int K, const int64_t* idx_err,
+                              int64_t total, int64_t* result, hipStream_t s);
+
 // ---- the reference's internal transpose steps (internals.hip) -------------
 // out[(j * lda + i) * es + t] = in[(i * ldb + j) * es + t]  (bshuf_trans_elem)
 hipError_t launch_trans_elem(const uint8_t* in, uint8_t* out, int64_t lda, int64_t ldb, int64_t es,

@@ -233,11 +233,14 @@ int bshuf_set_variant(int v) {
     // ticket shard runs out, | kNoOverlap (1 << 27): the pipelined encode's
     // parse launches all on the caller's stream, | kAltSegments (1 << 28): the
     // pipelined encode's other segment schedule, | kWideCompact (1 << 29): its
-    // side-stream compaction by the 256-thread k_compact (launch.h)
+    // side-stream compaction by the 256-thread k_compact (launch.h); and, read
+    // by the tile decode's gather alone (lz4_tile.hip), 4194304 / 8388608 /
+    // 12582912 (kTileLanes16 / 64 / 256): 16 / 64 / 256 lanes per row whatever
+    // the row's bytes
     const int vv = v & ~kSideBits;
     if (vv != 0 && vv != 2 && vv != 4 && vv != 8 && vv != 16 && vv != 32 && vv != 64 && vv != 128 && vv != 512 && vv != 1024 && vv != 2048 && vv != 4096 && vv != 8192 && vv != 16384 && vv != 24576 && vv != 40960 && vv != 57344 && vv != 65536 && vv != 319488 &&
         vv != 172032 && vv != 450560 &&
-        vv != 2793472 && vv != 3072000)
+        vv != 2793472 && vv != 3072000 && vv != kTileLanes16 && vv != kTileLanes64 && vv != kTileLanes256)
         return -71;
     t_variant = v;
     return 0;

@@ -1,9 +1,9 @@
 // Host build of the decoder's scan state machine (lz4_scan.h), of the
 // ticket-stealing arithmetic (ticket_steal.h), of the pipelined encode's
 // segment bounds (pipe_segments.h), of the range decode's piece plan
-// (range_plan.h), of the window decode's plan (window_plan.h) and of the
-// launchers' path decisions (dispatch.h) for the CPU test suite.  Not part of
-// the product library.
+// (range_plan.h), of the window decode's plan (window_plan.h), of the tile
+// decode's shape and plan (tile_plan.h) and of the launchers' path decisions
+// (dispatch.h) for the CPU test suite.  Not part of the product library.
 #include <stdint.h>
 
 #include "dispatch.h"
@@ -12,6 +12,7 @@
 #include "pipe_segments.h"
 #include "range_plan.h"
 #include "ticket_steal.h"
+#include "tile_plan.h"
 #include "window_plan.h"
 
 namespace {
@@ -133,6 +134,53 @@ extern "C" void bshuf_hostcheck_window_set_plan(int64_t count, const int64_t* si
                                w.t0, w.t1, 0};
         for (int j = 0; j < 12; j++) out[12 * i + j] = v[j];
     }
+}
+
+// tile_plan.h as the tile decode's host side uses it.  out[3]: rg, G, Mg.
+extern "C" void bshuf_hostcheck_tile_shape(int64_t rows, int64_t cols, int64_t pitch, int64_t bs, int64_t nb,
+                                           int64_t* out) {
+    bshuf::TileShape t;
+    bshuf::tile_shape(rows, cols, pitch, bs, nb, t);
+    out[0] = t.rg;
+    out[1] = t.G;
+    out[2] = t.Mg;
+}
+
+// ... and one tile as k_tile_plan and k_tile_gather run it, with the shape
+// tile_shape gives for nb blocks.  count < 0: the tile at `start` of ONE stream
+// of sizes[0] elements.  Else: of stream `id` of a set of `count` streams of
+// sizes[], whose stream `ref` (-1: none) serves a bad tile.  groups, 6 words per
+// group: the stream its blocks come from (0 for one stream, -1: none), b0,
+// nfull, last, bad, 0.  rowsout, 8 words per row (all 0 for a bad tile): g, lo, n,
+// tail_lo, tail_n (bytes), t0, t1, 0.  Returns the tile's bad flag.
+extern "C" int bshuf_hostcheck_tile_rows(int64_t count, const int64_t* sizes, int64_t id, int64_t ref,
+                                         int64_t bs, int64_t E, int64_t rows, int64_t cols, int64_t pitch,
+                                         int64_t nb, int64_t start, int64_t* groups, int64_t* rowsout) {
+    bshuf::TileShape t;
+    bshuf::tile_shape(rows, cols, pitch, bs, nb, t);
+    const int64_t span = (rows - 1) * pitch + cols;
+    const bool set = count >= 0;
+    const bool known = !set || (id >= 0 && id < count);
+    const int64_t size = known ? sizes[set ? id : 0] : 0;
+    const bool bad = set ? bshuf::tile_set_bad(count, id, size, bs, span, start, t.Mg)
+                         : bshuf::tile_bad(size, span, start);
+    int64_t s = set ? id : 0;
+    if (set && bad) s = ref >= 0 && ref < count ? ref : -1;
+    for (int64_t g = 0; g < t.G; g++) {
+        bshuf::WindowPlan w{};
+        w.nfull = t.Mg;
+        w.bad = 1;
+        if (s >= 0) bshuf::tile_group(sizes[s], bs, E, rows, cols, pitch, t, start, g, bad, w);
+        const int64_t v[6] = {s, w.b0, w.nfull, w.last, w.bad, 0};
+        for (int j = 0; j < 6; j++) groups[6 * g + j] = v[j];
+    }
+    for (int64_t r = 0; r < rows; r++) {
+        bshuf::TileRow o{};
+        if (!bad) bshuf::tile_row(bshuf::tile_covered(size, bs), bs, E, cols, pitch, t.rg, start, r, groups[6 * (r / t.rg) + 1], o);
+        const int64_t v[8] = {o.g, o.lo, o.n, o.tail_lo, o.tail_n, o.t0, o.t1, 0};
+        for (int j = 0; j < 8; j++) rowsout[8 * r + j] = v[j];
+    }
+    return bad ? 1 : 0;
 }
 
 // dispatch.h as the launchers use it.  The constants, out[14]: kTableBytes,

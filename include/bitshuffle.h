@@ -246,6 +246,74 @@ int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, si
                                              void* out, void* ws, size_t ws_bytes, int64_t* d_result,
                                              int64_t* d_status, void* stream);
 
+/* ---- tile decode: rows x cols crops at device-held corners (additive) ----
+ *
+ * Decodes `ntiles` tiles of rows x cols elements each, of ONE framed stream
+ * (bshuf_decompress_lz4_tiles_dev) or each of a stream of a stream set
+ * (bshuf_decompress_lz4_tiles_set_dev; d_set, count, max_size as for the window
+ * entry over a set).  The indices are flat, as for windows, and the array's
+ * shape is the caller's business: for a 2-D array of row length `pitch` a tile
+ * with its corner at (y, x) has start = y * pitch + x; for a stack of planes add
+ * the plane's offset.  d_starts (and d_ids) are DEVICE arrays of ntiles words,
+ * read by the kernels: row r of tile i is elements [d_starts[i] + r * pitch, ...
+ * + cols) of the stream (of stream d_ids[i]), and its cols * elem_size bytes
+ * land at out + ((i * rows + r) * cols) * elem_size (`out`: device, any byte
+ * alignment; nothing else of it is written).  The host never sees ids or
+ * starts: nothing is uploaded or read back, with a caller workspace nothing is
+ * allocated, the launches are one linear sequence on `stream`, and a call
+ * captured into a graph follows the arrays at every replay.
+ *
+ * With span = (rows - 1) * pitch + cols, every tile is cut into G = ceil(rows /
+ * rg) groups of rg consecutive rows (the last may hold fewer), and every group
+ * decodes Mg = min(((rg - 1) * pitch + cols + block_size - 2) / block_size + 1,
+ * blocks of the stream -- over a set: of its largest stream) consecutive blocks
+ * into a staging area of its own, from which its rows are copied.  rg is the one
+ * in 1..rows with the smallest G * Mg (of equal ones the largest): rows that
+ * share blocks are decoded together, rows that lie blocks apart are not
+ * connected by the blocks between them.  The workspace
+ * (bshuf_decompress_lz4_tiles_dev_workspace(...) /
+ * bshuf_decompress_lz4_tiles_set_dev_workspace(...) bytes, or NULL: library
+ * pool) holds ntiles * G staging areas of Mg blocks, per-tile, per-group and
+ * per-block tables and the token positions; its size depends on the arguments
+ * of these two functions alone.
+ *
+ * A tile is BAD when its start is outside [0, size - span]; over a set also
+ * when d_ids[i] is outside [0, count), span is above that stream's size, or the
+ * stream has fewer than Mg blocks (the window entry's rule).  A bad tile's
+ * bytes of `out` stay untouched.  d_status[i] (device, ntiles words, or NULL)
+ * is the first of these that applies: -71 for a bad tile; -91 (set) when the
+ * stream's rebuilt index failed; the code of the highest failing block, in
+ * stream order, among those that hold an element of the tile (blocks the tile
+ * merely lies between do not count: with an index supplied, a corrupt block no
+ * row touches does not fail the tile); -91 when a row reaches a verbatim tail
+ * that is not inside the stream; else rows * cols * elem_size.  A tile with a
+ * negative status is not written at all, not even its good rows.  *d_result
+ * (device) as for the window entries: -91 for a bad rebuilt index (single
+ * stream); else -71 when any tile was bad; else the status of the
+ * highest-numbered failing tile; else ntiles * rows * cols * elem_size.
+ *
+ * Returns 0 once enqueued (ntiles, rows or cols == 0: *d_result = 0, nothing is
+ * decoded).  Host errors: -81 for an invalid block_size; -71 for pitch < cols,
+ * span > size (set: > max_size), a block above the LDS decoder's size, ntiles *
+ * G * Mg >= 2^31 or ntiles * G >= 2^31, a workspace that is too small or not
+ * 256-byte aligned, d_set NULL or not 256-byte aligned; -70 without a device.
+ * The workspace functions return 0 for arguments the calls refuse. */
+size_t bshuf_decompress_lz4_tiles_dev_workspace(size_t in_nbytes, size_t size, size_t elem_size,
+                                                size_t block_size, size_t ntiles, size_t rows, size_t cols,
+                                                size_t pitch);
+int64_t bshuf_decompress_lz4_tiles_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                       size_t block_size, const int64_t* d_starts, size_t ntiles, size_t rows,
+                                       size_t cols, size_t pitch, void* out, void* ws, size_t ws_bytes,
+                                       int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
+                                       void* stream);
+size_t bshuf_decompress_lz4_tiles_set_dev_workspace(size_t max_size, size_t elem_size, size_t block_size,
+                                                    size_t ntiles, size_t rows, size_t cols, size_t pitch);
+int64_t bshuf_decompress_lz4_tiles_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                           size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                           size_t ntiles, size_t rows, size_t cols, size_t pitch, void* out,
+                                           void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                           void* stream);
+
 /* ---- batched device entry points (additive) ----
  *
  * `count` independent framed streams per call, all with the same elem_size and
