@@ -485,10 +485,33 @@ int64_t get_ws(void*& ws, size_t ws_bytes, size_t need, DevBuf& own, hipStream_t
 
 }  // namespace
 
+// Batches encoded one stream at a time: blocks above the LDS encoder's size,
+// or blocks of both LZ4 table types in one batch (a byU32-size block_size
+// with a byU16-size partial block).
+static bool enc_batch_per_stream(const BatchPlan& bp) {
+    const bool wide = (int64_t)bp.L.bs * bp.L.E >= kU16TableLimit;
+    bool mixed = (int64_t)bp.L.bs * bp.L.E > max_lds_encode_bytes();
+    for (const Seg& g : bp.segs) mixed = mixed || (g.last && ((int64_t)g.last * bp.L.E >= kU16TableLimit) != wide);
+    return mixed;
+}
+
+// ... their workspace: the largest single stream's (the streams follow each
+// other on the stream and take the workspace in turn).
+static size_t enc_per_stream_ws(const size_t* sizes, size_t count, size_t elem_size, size_t block_size) {
+    size_t need = 0;
+    for (size_t i = 0; i < count; i++) {
+        Plan p;
+        if (make_plan(sizes[i], elem_size, block_size, p)) return 0;
+        need = std::max(need, enc_ws(p, nullptr, nullptr));
+    }
+    return need;
+}
+
 size_t bshuf_compress_lz4_batch_dev_workspace(const size_t* sizes, size_t count, size_t elem_size,
                                               size_t block_size) {
     BatchPlan bp;
     if (make_batch(nullptr, nullptr, sizes, nullptr, count, elem_size, block_size, bp)) return 0;
+    if (enc_batch_per_stream(bp)) return enc_per_stream_ws(sizes, count, elem_size, block_size);
     return enc_batch_ws(bp, nullptr, nullptr, nullptr, nullptr);
 }
 
@@ -502,14 +525,12 @@ static int64_t compress_batch(const void* const* in, void* const* out, const siz
     if (!have_device()) return kErrHip;
     hipStream_t s = (hipStream_t)stream;
     for (size_t i = 0; i < count; i++) bp.segs[i].result = d_results + i;
-    // blocks of both LZ4 table types in one batch (a byU32-size block_size
-    // with a byU16-size partial block): one stream at a time
-    const bool wide = (int64_t)bp.L.bs * bp.L.E >= kU16TableLimit;
-    bool mixed = (int64_t)bp.L.bs * bp.L.E > max_lds_encode_bytes();  // large blocks: per stream
-    for (const Seg& g : bp.segs) mixed = mixed || (g.last && ((int64_t)g.last * bp.L.E >= kU16TableLimit) != wide);
-    if (mixed) {
+    if (enc_batch_per_stream(bp)) {
+        // one stream at a time, each in the caller's workspace when there is one
+        if (ws && (ws_bytes < enc_per_stream_ws(sizes, count, elem_size, block_size) || ((uintptr_t)ws & 255)))
+            return kErrUnsupported;
         for (size_t i = 0; i < count; i++) {
-            const int64_t e = compress_dev(in[i], out[i], sizes[i], elem_size, block_size, nullptr, 0,
+            const int64_t e = compress_dev(in[i], out[i], sizes[i], elem_size, block_size, ws, ws ? ws_bytes : 0,
                                            d_results + i,
                                            block_offsets ? block_offsets + bp.segs[i].first : nullptr,
                                            stream, fast);
@@ -549,10 +570,22 @@ int64_t bshuf_compress_lz4_fast_batch_dev(const void* const* in, void* const* ou
                           block_offsets, stream, true);
 }
 
+// Blocks above the LDS decoder's size are decoded one stream at a time, in a
+// workspace of the largest single stream's size (as the encoder's, above).
+static size_t dec_per_stream_ws(const size_t* in_nbytes, const size_t* sizes, size_t count, size_t elem_size,
+                                size_t block_size) {
+    size_t need = 0;
+    for (size_t i = 0; i < count; i++)
+        need = std::max(need, bshuf_decompress_lz4_dev_workspace(in_nbytes[i], sizes[i], elem_size, block_size));
+    return need;
+}
+
 size_t bshuf_decompress_lz4_batch_dev_workspace(const size_t* in_nbytes, const size_t* sizes,
                                                 size_t count, size_t elem_size, size_t block_size) {
     BatchPlan bp;
     if (make_batch(nullptr, nullptr, sizes, in_nbytes, count, elem_size, block_size, bp)) return 0;
+    if ((int64_t)bp.L.bs * bp.L.E > max_lds_decode_bytes())
+        return dec_per_stream_ws(in_nbytes, sizes, count, elem_size, block_size);
     return dec_batch_ws(bp, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
@@ -569,10 +602,14 @@ static int64_t decompress_batch(const void* const* in, const size_t* in_nbytes, 
     hipStream_t s = (hipStream_t)stream;
     for (size_t i = 0; i < count; i++) bp.segs[i].result = d_results + i;
     if ((int64_t)bp.L.bs * bp.L.E > max_lds_decode_bytes()) {
-        // blocks above the LDS decoder's size: one stream at a time
+        // blocks above the LDS decoder's size: one stream at a time, each in
+        // the caller's workspace when there is one
+        if (ws && (ws_bytes < dec_per_stream_ws(in_nbytes, sizes, count, elem_size, block_size) ||
+                   ((uintptr_t)ws & 255)))
+            return kErrUnsupported;
         for (size_t i = 0; i < count; i++) {
             const int64_t e = decompress_dev(in[i], in_nbytes[i], dlens ? dlens + i : nullptr, out[i],
-                                             sizes[i], elem_size, block_size, nullptr, 0, d_results + i,
+                                             sizes[i], elem_size, block_size, ws, ws ? ws_bytes : 0, d_results + i,
                                              nullptr, stream);
             if (e) return e;
         }

@@ -541,6 +541,26 @@ struct TableStage {
 };
 thread_local TableStage t_table;
 
+// Pinned memory for a captured upload.  A capture in hipStreamCaptureModeGlobal
+// (what torch.cuda.graph and most callers use) refuses allocation calls on
+// every thread and invalidates the capture; the allocation touches no stream,
+// so the thread's capture mode is relaxed around it and put back.
+hipError_t captured_host_alloc(void** host, void** dev, size_t bytes) {
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    hipError_t e = hipThreadExchangeStreamCaptureMode(&mode);
+    if (e != hipSuccess) return e;
+    e = hipHostMalloc(host, bytes, hipHostMallocCoherent | hipHostMallocMapped);
+    if (e == hipSuccess) {
+        e = hipHostGetDevicePointer(dev, *host, 0);
+        if (e != hipSuccess) {
+            (void)hipHostFree(*host);
+            *host = nullptr;
+        }
+    }
+    (void)hipThreadExchangeStreamCaptureMode(&mode);
+    return e;
+}
+
 // The flag word of captured uploads (written at every replay, never read).
 uint32_t* t_captured_flags() {
     static uint32_t* dev = nullptr;
@@ -551,8 +571,7 @@ uint32_t* t_captured_flags() {
     if (!made.load(std::memory_order_relaxed)) {
         void* h = nullptr;
         void* d = nullptr;
-        if (hipHostMalloc(&h, 64, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess &&
-            hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
+        if (captured_host_alloc(&h, &d, 64) == hipSuccess) {
             dev = (uint32_t*)d;
             made.store(true, std::memory_order_release);
         }
@@ -574,8 +593,8 @@ hipError_t stage_upload(const void* host, size_t bytes, void* dev, hipStream_t s
         // captured: a buffer of its own, kept for the graph's replays
         void* h = nullptr;
         void* d = nullptr;
-        if (hipHostMalloc(&h, bytes + 64, fl) != hipSuccess) return hipErrorOutOfMemory;
-        if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) return hipErrorUnknown;
+        const hipError_t e = captured_host_alloc(&h, &d, bytes + 64);
+        if (e != hipSuccess) return e;
         memcpy(h, host, bytes);
         XferArgs a{(uint8_t*)dev, (const uint8_t*)d, (int64_t)bytes, t_captured_flags(), 1};
         if (!a.flags) return hipErrorOutOfMemory;

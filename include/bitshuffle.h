@@ -326,7 +326,13 @@ int64_t bshuf_decompress_lz4_tiles_set_dev(const void* d_set, size_t count, size
  * A corrupt stream never affects the others.  block_offsets (optional,
  * device, one u64 per block of the batch in stream order): each block's
  * header offset inside its own stream.  The per-stream table travels through a
- * per-thread pinned buffer; nothing synchronises the host.
+ * per-thread pinned buffer; nothing synchronises the host.  Batches that run
+ * one stream at a time (blocks above the LDS kernels' size; encode: streams
+ * that need both LZ4 table types) take each stream through the caller's
+ * workspace in turn: the _workspace functions return the largest single
+ * stream's need for them, and with a workspace nothing is allocated.  (These
+ * batches used to ignore `ws` and take pool memory: a workspace smaller than
+ * the _workspace function now returns is refused with -71 for them too.)
  */
 size_t bshuf_compress_lz4_batch_dev_workspace(const size_t* sizes, size_t count, size_t elem_size,
                                               size_t block_size);
