@@ -39,6 +39,14 @@ a failing block is not written at all
     decompress_lz4_tiles_workspace(in_nbytes, size, elem_size, ntiles, rows, cols, pitch, ...)
     decompress_lz4_tiles_set_dev(sset, dtype, ids, starts, rows, cols, pitch, ...) -> (K, rows, cols)
     decompress_lz4_tiles_set_workspace(sset, ntiles, rows, cols, pitch, ...)
+Ragged window decode (device): K windows whose starts AND counts are DEVICE
+tensors, bounded by max_window; packed back to back with an offsets tensor
+(values + offsets), or one per row of a (K, pitch) output
+    decompress_lz4_ragged_dev(buf, size, dtype, starts, counts, max_window, ...)
+        -> (out, out_offsets, status)
+    decompress_lz4_ragged_workspace(in_nbytes, size, elem_size, nwindows, max_window, ...)
+    decompress_lz4_ragged_set_dev(sset, dtype, ids, starts, counts, max_window, ...)
+    decompress_lz4_ragged_set_workspace(sset, nwindows, max_window, ...)
 """
 from ._lib import (  # noqa: F401
     LIB_PATH,
@@ -64,6 +72,10 @@ from .api import (  # noqa: F401
     decompress_lz4,
     decompress_lz4_batch_dev,
     decompress_lz4_dev,
+    decompress_lz4_ragged_dev,
+    decompress_lz4_ragged_set_dev,
+    decompress_lz4_ragged_set_workspace,
+    decompress_lz4_ragged_workspace,
     decompress_lz4_range_dev,
     decompress_lz4_ranges_dev,
     decompress_lz4_ranges_workspace,
@@ -109,6 +121,10 @@ __all__ = [
     "lz4_stream_set_dev",
     "decompress_lz4_windows_set_dev",
     "decompress_lz4_windows_set_workspace",
+    "decompress_lz4_ragged_dev",
+    "decompress_lz4_ragged_workspace",
+    "decompress_lz4_ragged_set_dev",
+    "decompress_lz4_ragged_set_workspace",
     "decompress_lz4_tiles_dev",
     "decompress_lz4_tiles_workspace",
     "decompress_lz4_tiles_set_dev",

@@ -56,6 +56,12 @@ PROTOTYPES = {
     "bshuf_decompress_lz4_windows_set_dev_workspace": (_sz, [_sz, _sz, _sz, _sz, _sz]),
     "bshuf_decompress_lz4_windows_set_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _vp,
                                                     _sz, _vp, _vp, _vp]),
+    "bshuf_decompress_lz4_ragged_dev_workspace": (_sz, [_sz, _sz, _sz, _sz, _sz, _sz]),
+    "bshuf_decompress_lz4_ragged_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp,
+                                               _vp, _sz, _vp, _vp, _vp, _vp]),
+    "bshuf_decompress_lz4_ragged_set_dev_workspace": (_sz, [_sz, _sz, _sz, _sz, _sz]),
+    "bshuf_decompress_lz4_ragged_set_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _sz,
+                                                   _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
     "bshuf_decompress_lz4_tiles_dev_workspace": (_sz, [_sz, _sz, _sz, _sz, _sz, _sz, _sz, _sz]),
     "bshuf_decompress_lz4_tiles_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _sz,
                                               _vp, _vp, _vp, _vp]),

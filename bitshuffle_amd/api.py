@@ -501,6 +501,121 @@ def decompress_lz4_windows_set_dev(sset, dtype, ids, starts, window, out=None, w
                         workspace, result, status, sync, elem_size, holds=sset.elem_size)
 
 
+def _ragged_dev(call, device, whose, index, dtype, max_window, out, out_offsets, pitch, workspace, result,
+                status, sync, elem_size, holds=None):
+    """What the ragged decodes of one stream and of a set share, as _windows_dev
+    for the window decodes.  call(es, K, max_window, out, capacity, pitch,
+    out_offsets, ws, ws_bytes, result, status) makes the library call."""
+    torch = _torch()
+    for name, t in index:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+                and t.device == device):
+            raise ValueError("%s must be a contiguous int64 tensor on the %s device" % (name, whose))
+    counts = [t.numel() for _, t in index]
+    if len(set(counts)) > 1:
+        raise ValueError("%s need one entry per window (%s)" % (", ".join(name for name, _ in index),
+                                                                ", ".join("%d" % n for n in counts)))
+    K, max_window, pitch = counts[-1], int(max_window), int(pitch)
+    if max_window < 0 or pitch < 0:
+        raise ValueError("max_window and pitch must be >= 0, not %d and %d" % (max_window, pitch))
+    per = 1 if elem_size is None else int(elem_size)  # out items per element
+    if out is None:
+        shape = (K, pitch * per) if pitch else (K * max_window * per,)
+        out = torch.empty(shape, dtype=dtype if elem_size is None else torch.uint8, device=device)
+    es = out.element_size() if elem_size is None else int(elem_size)
+    if holds is not None and es != holds:
+        raise ValueError("the set holds %d-byte elements, not %d-byte ones" % (holds, es))
+    capacity = out.numel() * out.element_size() // es
+    if out_offsets is None:
+        out_offsets = torch.empty(K + 1, dtype=torch.int64, device=device)
+    if out_offsets.dtype != torch.int64 or out_offsets.numel() < K + 1 or not out_offsets.is_contiguous():
+        raise ValueError("out_offsets must be a contiguous int64 tensor of %d entries" % (K + 1))
+    if status is None:
+        status = torch.empty(K, dtype=torch.int64, device=device)
+    if status.dtype != torch.int64 or status.numel() < K:
+        raise ValueError("status must be an int64 tensor of %d entries" % K)
+    if result is None:
+        result = torch.empty(1, dtype=torch.int64, device=device)
+    ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+    wsb = workspace.numel() if workspace is not None else 0
+    _check(call(es, K, max_window, _dptr(out), capacity, pitch, _dptr(out_offsets), ws, wsb, _dptr(result),
+                _dptr(status)))
+    if not sync:
+        return out, out_offsets, status, result
+    count = int(result.item())
+    if count < 0:
+        _fail(count)
+    return out, out_offsets, status
+
+
+def decompress_lz4_ragged_workspace(in_nbytes, size, elem_size, nwindows, max_window, block_size=0,
+                                    device=None):
+    """A workspace for decompress_lz4_ragged_dev of `nwindows` windows of at
+    most `max_window` elements of a stream of `in_nbytes` bytes: its size
+    depends on these numbers only, never on the starts or the counts."""
+    torch = _torch()
+    n = int(lib.bshuf_decompress_lz4_ragged_dev_workspace(in_nbytes, size, elem_size, block_size, nwindows,
+                                                          max_window))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device or "cuda")
+
+
+def decompress_lz4_ragged_dev(buf, size, dtype, starts, counts, max_window, out=None, out_offsets=None,
+                              pitch=0, block_size=0, workspace=None, result=None, status=None, offsets=None,
+                              stream=None, sync=True, elem_size=None):
+    """Ragged window decode (bshuf_decompress_lz4_ragged_dev): window i is
+    elements [starts[i], starts[i] + counts[i]) of the framed stream in uint8
+    device tensor `buf`, which encodes `size` elements of `dtype`.  `starts` and
+    `counts` are contiguous int64 DEVICE tensors of equal length K, read by the
+    kernels only; `max_window` bounds the counts and, with K, fixes the call's
+    shape, so a call captured into a graph follows both tensors at every replay.
+    pitch == 0: the windows land back to back in the flat `out` (allocated with
+    K * max_window elements when None), window i at element out_offsets[i] --
+    `out_offsets` (int64 device tensor, K + 1 entries) receives the exclusive
+    scan of the good windows' counts.  pitch >= max_window: window i lands in
+    row i of a (K, pitch) `out`, the rest of the row untouched.  A window with
+    a count outside [0, max_window] or a start outside [0, size - count], or
+    one that does not fit a packed `out`, is refused: status -71, nothing
+    written.  Returns (out, out_offsets, status) (sync=True, which reads only
+    `result`), or (out, out_offsets, status, result) (sync=False).  `status`
+    (int64 device tensor, K entries): per window its byte count, -71, or the
+    code of a failing block that holds elements of it.  `offsets`: the stream's
+    block index; without it the index is rebuilt from the whole stream."""
+    def call(es, K, max_window, outp, capacity, pitch, *ptrs):
+        offp = _dptr(offsets) if offsets is not None else None
+        return lib.bshuf_decompress_lz4_ragged_dev(_dptr(buf), buf.numel(), int(size), es, block_size,
+                                                   _dptr(starts), _dptr(counts), K, max_window, outp, capacity,
+                                                   pitch, *ptrs, offp, _stream(stream))
+    return _ragged_dev(call, buf.device, "stream's", [("starts", starts), ("counts", counts)], dtype,
+                       max_window, out, out_offsets, pitch, workspace, result, status, sync, elem_size)
+
+
+def decompress_lz4_ragged_set_workspace(sset, nwindows, max_window, device=None):
+    """A workspace for decompress_lz4_ragged_set_dev of `nwindows` windows of at
+    most `max_window` elements over StreamSet `sset`."""
+    torch = _torch()
+    n = int(lib.bshuf_decompress_lz4_ragged_set_dev_workspace(sset.max_size, sset.elem_size, sset.block_size,
+                                                              nwindows, max_window))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device or sset.device)
+
+
+def decompress_lz4_ragged_set_dev(sset, dtype, ids, starts, counts, max_window, out=None, out_offsets=None,
+                                  pitch=0, workspace=None, result=None, status=None, stream=None, sync=True,
+                                  elem_size=None):
+    """Ragged window decode over a StreamSet (bshuf_decompress_lz4_ragged_set_dev):
+    window i is elements [starts[i], starts[i] + counts[i]) of stream ids[i];
+    everything else as decompress_lz4_ragged_dev.  An id outside the set refuses
+    the window (-71); a stream of any number of blocks takes windows, also one
+    with fewer blocks than a window of max_window elements may touch."""
+    def call(es, K, max_window, outp, capacity, pitch, *ptrs):
+        return lib.bshuf_decompress_lz4_ragged_set_dev(_dptr(sset.table), sset.count, sset.max_size, es,
+                                                       sset.block_size, _dptr(ids), _dptr(starts),
+                                                       _dptr(counts), K, max_window, outp, capacity, pitch,
+                                                       *ptrs, _stream(stream))
+    return _ragged_dev(call, sset.device, "set's", [("ids", ids), ("starts", starts), ("counts", counts)],
+                       dtype, max_window, out, out_offsets, pitch, workspace, result, status, sync, elem_size,
+                       holds=sset.elem_size)
+
+
 def _tiles_dev(call, device, whose, index, dtype, rows, cols, pitch, out, workspace, result, status, sync,
                elem_size, holds=None):
     """What the tile decodes of one stream and of a set share, as _windows_dev

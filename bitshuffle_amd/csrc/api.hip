@@ -1320,6 +1320,198 @@ int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, si
 }
 
 // ---------------------------------------------------------------------------
+// ragged windows: device-held starts and lengths, of one stream or of a set,
+// packed (values + offsets) or at a fixed pitch
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// The window decode's buffers for windows of max_window elements, and behind
+// them the placement scan's.
+struct RaggedBufs {
+    WindowBufs w;
+    int64_t* offs;  // K + 1: the windows' places, when the caller passes no d_out_offsets
+    int64_t* sums;  // the scan's tile sums
+};
+
+size_t ragged_ws(const Plan& p, const WindowShape& w, int64_t blocks_end, RaggedBufs* b, uint8_t* base) {
+    RaggedBufs x{};
+    Carver c{base};
+    c.off = window_ws(p, w, blocks_end, &x.w, base);
+    x.offs = c.take<int64_t>(((size_t)w.K + 1) * 8);
+    x.sums = c.take<int64_t>((size_t)kRaggedScanTiles * 8);
+    if (b) *b = x;
+    return c.off;
+}
+
+// What the host refuses of the output's description.
+int64_t ragged_output(size_t nwindows, size_t max_window, size_t out_capacity, size_t out_pitch,
+                      const int64_t* d_out_offsets) {
+    if (out_capacity >= ((uint64_t)1 << 62) || out_pitch >= ((uint64_t)1 << 62)) return kErrUnsupported;
+    if (out_pitch == 0) return d_out_offsets ? 0 : kErrUnsupported;
+    if (out_pitch < max_window) return kErrUnsupported;
+    if (nwindows && out_pitch > out_capacity / nwindows) return kErrUnsupported;
+    return 0;
+}
+
+// Nothing to decode (no windows, or none longer than 0): result 0, offsets 0.
+int64_t ragged_empty(size_t nwindows, int64_t* d_out_offsets, int64_t* d_result, hipStream_t s) {
+    if (dev_fill(d_result, 0, sizeof(int64_t), s) != hipSuccess) return kErrHip;
+    if (d_out_offsets && dev_fill(d_out_offsets, 0, (nwindows + 1) * sizeof(int64_t), s) != hipSuccess)
+        return kErrHip;
+    return 0;
+}
+
+// What the two ragged entry points share, from the workspace to the result:
+// one linear chain on s.  make_source(b): the call's source, with what of it
+// lies in the workspace.  index(src, b, idx_err): the source's index rebuild,
+// if it has one (idx_err: its error word).
+extern "C++" template <class MakeSource, class Index>
+int64_t ragged_decode(const Plan& p, const WindowShape& w, int64_t blocks_end, size_t need,
+                      const int64_t* d_starts, const int64_t* d_counts, void* out, size_t out_capacity,
+                      size_t out_pitch, int64_t* d_out_offsets, void* ws, size_t ws_bytes, int64_t* d_result,
+                      int64_t* d_status, hipStream_t s, MakeSource make_source, Index index) {
+    DevBuf own;
+    const int64_t r = get_ws(ws, ws_bytes, need, own, s);
+    if (r) return r;
+    RaggedBufs rb;
+    ragged_ws(p, w, blocks_end, &rb, (uint8_t*)ws);
+    const WindowBufs& b = rb.w;
+    const int K = (int)w.K;
+    int64_t* wstat = d_status ? d_status : b.wstat;
+
+    auto src = make_source(b);
+    RaggedCall c{};
+    c.w.starts = d_starts;
+    c.w.out = (uint8_t*)out;
+    c.w.slots = b.slots;
+    c.w.res = b.res;
+    c.w.window = w.window;
+    c.w.wbytes = w.window * p.L.E;
+    c.w.slot = w.slot;
+    c.w.Mw = w.Mw;
+    c.w.seq_words = w.shared_seq ? -1 : w.pw;
+    c.w.bs = p.L.bs;
+    c.w.E = p.L.E;
+    c.w.K = K;
+    c.counts = d_counts;
+    c.offs = d_out_offsets ? d_out_offsets : rb.offs;
+    c.capacity = (int64_t)out_capacity;
+    c.pitch = (int64_t)out_pitch;
+    if (launch_ragged_scan(src, c, rb.sums, s) != hipSuccess ||
+        launch_ragged_plan(src, c, b.segs, b.pcs, b.wt, s) != hipSuccess)
+        return kErrHip;
+    const int64_t* idx_err = nullptr;
+    if (index(src, b, idx_err) != hipSuccess) return kErrHip;
+    if (w.Mw > 0) {
+        // as window_decode: one scan and one decode launch over all K * Mw work
+        // blocks, most of them inert when the windows are short
+        Layout L = p.L;
+        L.nfull = w.K * w.Mw;
+        L.last = 0;
+        if (dev_fill(b.d.idx_err, 0, (size_t)K * 8, s) != hipSuccess ||
+            launch_ragged_worklist(src, c, b.segs, b.pcs, b.wt, b.d.offs, b.blk_seg, s) != hipSuccess ||
+            launch_decode_batch(b.segs, nullptr, K, b.blk_seg, L, b.d, s) != hipSuccess)
+            return kErrHip;
+    }
+    if (launch_ragged_gather(src, c, b.pcs, b.wt, b.d.status, wstat, s) != hipSuccess ||
+        launch_window_reduce(wstat, b.wt, K, idx_err, p.L.E, d_result, s, c.offs + K) != hipSuccess)
+        return kErrHip;
+    return 0;
+}
+
+}  // namespace
+
+size_t bshuf_decompress_lz4_ragged_dev_workspace(size_t in_nbytes, size_t size, size_t elem_size,
+                                                 size_t block_size, size_t nwindows, size_t max_window) {
+    Plan p;
+    WindowShape w;
+    if (make_plan(size, elem_size, block_size, p) ||
+        window_shape(p, size, in_nbytes, nwindows, max_window, false, w))
+        return 0;
+    const int64_t cb = (int64_t)in_nbytes - p.tail;
+    return ragged_ws(p, w, cb > 0 ? cb : 0, nullptr, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_ragged_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                        size_t block_size, const int64_t* d_starts, const int64_t* d_counts,
+                                        size_t nwindows, size_t max_window, void* out, size_t out_capacity,
+                                        size_t out_pitch, int64_t* d_out_offsets, void* ws, size_t ws_bytes,
+                                        int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
+                                        void* stream) {
+    Plan p;
+    int64_t r = make_plan(size, elem_size, block_size, p);
+    if (r) return r;
+    WindowShape w;
+    r = window_shape(p, size, in_nbytes, nwindows, max_window, false, w);
+    if (r) return r;
+    r = ragged_output(nwindows, max_window, out_capacity, out_pitch, d_out_offsets);
+    if (r) return r;
+    int64_t cb = (int64_t)in_nbytes - p.tail;
+    if (cb < 0) cb = 0;
+    const size_t need = ragged_ws(p, w, cb, nullptr, nullptr);
+    if (ws && (ws_bytes < need || ((uintptr_t)ws & 255))) return kErrUnsupported;
+    if (!have_device()) return kErrHip;
+    hipStream_t s = (hipStream_t)stream;
+    if (nwindows == 0 || max_window == 0) return ragged_empty(nwindows, d_out_offsets, d_result, s);
+    const uint8_t* i8 = (const uint8_t*)in;
+    return ragged_decode(
+        p, w, cb, need, d_starts, d_counts, out, out_capacity, out_pitch, d_out_offsets, ws, ws_bytes, d_result,
+        d_status, s,
+        // the scan and the plan read the stream's address and size only: the index comes behind them
+        [&](const WindowBufs&) { return WindowStream{RangeStream{i8}, (int64_t)size}; },
+        [&](WindowStream& src, const WindowBufs& b, const int64_t*& idx_err) {
+            return stream_with_index(i8, in_nbytes, cb, p, block_offsets, b.idx, s, src.st, idx_err);
+        });
+}
+
+size_t bshuf_decompress_lz4_ragged_set_dev_workspace(size_t max_size, size_t elem_size, size_t block_size,
+                                                     size_t nwindows, size_t max_window) {
+    Plan p;
+    WindowShape w;
+    if (make_plan(max_size, elem_size, block_size, p) ||
+        window_shape(p, max_size, 0, nwindows, max_window, true, w))
+        return 0;
+    return ragged_ws(p, w, 0, nullptr, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_ragged_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                            size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                            const int64_t* d_counts, size_t nwindows, size_t max_window,
+                                            void* out, size_t out_capacity, size_t out_pitch,
+                                            int64_t* d_out_offsets, void* ws, size_t ws_bytes,
+                                            int64_t* d_result, int64_t* d_status, void* stream) {
+    Plan p;
+    int64_t r = make_plan(max_size, elem_size, block_size, p);
+    if (r) return r;
+    WindowShape w;
+    r = window_shape(p, max_size, 0, nwindows, max_window, true, w);
+    if (r) return r;
+    r = ragged_output(nwindows, max_window, out_capacity, out_pitch, d_out_offsets);
+    if (r) return r;
+    if (count > (size_t)INT32_MAX) return kErrUnsupported;
+    const size_t need = ragged_ws(p, w, 0, nullptr, nullptr);
+    if (ws && (ws_bytes < need || ((uintptr_t)ws & 255))) return kErrUnsupported;
+    if (!d_set || ((uintptr_t)d_set & 255)) return kErrUnsupported;
+    if (!have_device()) return kErrHip;
+    hipStream_t s = (hipStream_t)stream;
+    if (nwindows == 0 || max_window == 0) return ragged_empty(nwindows, d_out_offsets, d_result, s);
+    return ragged_decode(
+        p, w, 0, need, d_starts, d_counts, out, out_capacity, out_pitch, d_out_offsets, ws, ws_bytes, d_result,
+        d_status, s,
+        [&](const WindowBufs& b) {
+            return WindowSet{(const StreamSetHeader*)d_set,
+                             (const StreamSetRec*)((const uint8_t*)d_set + kStreamSetRecs),
+                             d_ids,
+                             b.sidx,
+                             (int64_t)count,
+                             p.nb};
+        },
+        // (the set's indexes were made by its build: nothing to rebuild)
+        [&](const WindowSet&, const WindowBufs&, const int64_t*&) { return hipSuccess; });
+}
+
+// ---------------------------------------------------------------------------
 // rows x cols tiles at device-held flat starts, of one stream or of a set
 // ---------------------------------------------------------------------------
 

@@ -380,9 +380,52 @@ hipError_t launch_window_gather(const Source& src, const WindowCall& c, const Ra
                                 const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s);
 // *result = -91 when *idx_err (nullptr: no index was rebuilt by the call) is set,
 // else -71 when a window was bad, else the status of the highest-numbered
-// failing window, else K * wbytes.
+// failing window, else total (K * wbytes) -- or, with dtotal, `total` bytes for
+// each of the *dtotal elements of a device-held count (the ragged decode).
 hipError_t launch_window_reduce(const int64_t* wstat, const WindowTail* wt, int K, const int64_t* idx_err,
-                                int64_t total, int64_t* result, hipStream_t s);
+                                int64_t total, int64_t* result, hipStream_t s, const int64_t* dtotal = nullptr);
+
+// ---- ragged window decode (lz4_ragged.hip) ---------------------------------
+// K windows at DEVICE-held starts AND lengths (bshuf_decompress_lz4_ragged_dev,
+// bshuf_decompress_lz4_ragged_set_dev); the host knows max_window, a bound on
+// the lengths, which with K fixes every table of the window decode: window i is
+// still one Seg of Mw work blocks with a staging area of its own.  What differs:
+// k_ragged_scan places the windows in the output (the exclusive scan of their
+// lengths, 0 for a refused one; window_plan.h, ragged_good) and k_ragged_plan
+// plans each with its own length (ragged_plan).  Of a window's Mw work blocks
+// only [t0, t1) hold bytes of it; k_ragged_worklist gives those their header
+// offsets and every other one the sentinel (kNoOffset, range_worklist.h), and
+// narrows the window's readable bytes to the live blocks' records, so nothing of
+// a block the window does not need is read, and such a block's failure is not
+// the window's.  It also writes the block -> window map over all Mw work blocks
+// (launch_seg_map would stop at the blocks a short stream of a set has).  The
+// token scan and the block decode run unchanged; k_ragged_gather is
+// k_window_gather with the window's own byte count, the reduce k_window_reduce
+// with the total read from the scan's last entry.
+struct RaggedCall {
+    WindowCall w;           // (w.window: max_window; w.wbytes: max_window * E; w.out: the output's base)
+    const int64_t* counts;  // device, K element counts
+    int64_t* offs;          // device, K + 1: the exclusive scan of the good windows' counts
+    int64_t capacity;       // elements of the output
+    int64_t pitch;          // 0: packed, window i at element offs[i]; else at i * pitch
+};
+constexpr int kRaggedScanTiles = 1024;  // tile sums of the placement scan (workspace)
+// offs[0 .. K] from the starts and counts (and ids); sums: kRaggedScanTiles words.
+template <class Source>
+hipError_t launch_ragged_scan(const Source& src, const RaggedCall& c, int64_t* sums, hipStream_t s);
+// Seg, RangePiece, WindowTail and (set) src.sidx entry i; a refused window, or
+// one that has no room in a packed output, has no stream bytes to read at all.
+template <class Source>
+hipError_t launch_ragged_plan(const Source& src, const RaggedCall& c, Seg* segs, RangePiece* pcs,
+                              WindowTail* wt, hipStream_t s);
+// wl and blk_seg over the K * Mw work blocks, every Seg's in_nbytes and seq0.
+template <class Source>
+hipError_t launch_ragged_worklist(const Source& src, const RaggedCall& c, Seg* segs, const RangePiece* pcs,
+                                  const WindowTail* wt, uint64_t* wl, uint32_t* blk_seg, hipStream_t s);
+// launch_window_gather's rule, window i's byte count being counts[i] * E.
+template <class Source>
+hipError_t launch_ragged_gather(const Source& src, const RaggedCall& c, const RangePiece* pcs,
+                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s);
 
 // ---- tile decode (lz4_tile.hip) -------------------------------------------
 // K tiles of rows x cols elements at DEVICE-held flat starts, row r of tile i

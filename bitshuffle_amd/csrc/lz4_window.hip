@@ -48,22 +48,6 @@ __device__ __forceinline__ const uint8_t* source_plan(const WindowSet& src, cons
     return s >= 0 ? src.recs[s].st.in : (const uint8_t*)src.hdr;  // (never read without a stream)
 }
 
-// For the gather: window i's stream and that stream's error word.
-__device__ __forceinline__ RangeStream source_stream(const WindowStream& src, const WindowTail&, int,
-                                                     int64_t& err) {
-    err = 0;
-    return src.st;
-}
-
-__device__ __forceinline__ RangeStream source_stream(const WindowSet& src, const WindowTail& w, int i,
-                                                     int64_t& err) {
-    err = 0;
-    if (w.bad) return RangeStream{};
-    const StreamSetRec r = src.recs[src.sidx[i]];
-    err = r.err;
-    return r.st;
-}
-
 // ProfScope names: the ones the two calls had with kernels of their own.
 struct Names {
     const char *plan, *gather;
@@ -72,47 +56,6 @@ constexpr Names names(const WindowStream&) { return {"k_window_plan", "k_window_
 constexpr Names names(const WindowSet&) { return {"k_window_set_plan", "k_window_set_gather"}; }
 
 // ---- the kernels ----------------------------------------------------------
-// Window i's Seg (Mw consecutive blocks of the stream at `in`, decoded back to
-// back into staging area i), its piece (the clip of that area) and its tail span.
-__device__ __forceinline__ void write_window(const WindowCall& c, int i, const WindowPlan& w, const uint8_t* in,
-                                             Seg* __restrict__ segs, RangePiece* __restrict__ pcs,
-                                             WindowTail* __restrict__ wt) {
-    uint8_t* slot = c.slots + (int64_t)i * c.slot;
-    Seg g;
-    g.in = in;
-    g.out = slot;
-    g.first = (int64_t)i * c.Mw;
-    g.nfull = w.nfull;
-    g.tail = 0;
-    g.in_nbytes = 0;  // the work list: the end of the window's last record
-    g.chunk0 = 0;
-    g.nchunks = 0;
-    g.seq0 = 0;       // the work list
-    g.result = c.res + i;
-    g.last = w.last;
-    g.pad_ = 0;
-    segs[i] = g;
-    RangePiece pc;
-    pc.b0 = w.b0;
-    pc.nblk = c.Mw;
-    pc.seq_base = c.seq_words < 0 ? -1 : (int64_t)i * c.seq_words;
-    pc.src = slot + w.clip_lo;
-    pc.dst = c.out + (int64_t)i * c.wbytes;
-    pc.lo = 0;
-    pc.n = w.clip_n;
-    pc.kind = kPieceEdge;
-    pc.pad_ = 0;
-    pcs[i] = pc;
-    WindowTail t;
-    t.lo = w.tail_lo;
-    t.n = w.tail_n;
-    t.t0 = (int32_t)w.t0;
-    t.t1 = (int32_t)w.t1;
-    t.bad = w.bad;
-    t.pad_ = 0;
-    wt[i] = t;
-}
-
 // One thread per window.  A bad window of one stream (start out of range) gets
 // block 0 on and nothing to copy.
 template <class Source>
@@ -123,7 +66,7 @@ __global__ __launch_bounds__(256) void k_window_plan(Source src, WindowCall c, S
     if (i >= c.K) return;
     WindowPlan w;
     const uint8_t* in = source_plan(src, c, i, w);
-    write_window(c, i, w, in, segs, pcs, wt);
+    write_window(c, i, w, in, c.out + (int64_t)i * c.wbytes, segs, pcs, wt);
 }
 
 // Workgroups (p, 0 .. gridDim.y) share window p's Mw work blocks.
@@ -180,7 +123,7 @@ __global__ __launch_bounds__(256) void k_stream_set_status(StreamSetRec* __restr
 __global__ __launch_bounds__(256) void k_window_reduce(const int64_t* __restrict__ wstat,
                                                        const WindowTail* __restrict__ wt, int K,
                                                        const int64_t* idx_err, int64_t total,
-                                                       int64_t* result) {
+                                                       const int64_t* dtotal, int64_t* result) {
     __shared__ int bad, oob;
     if (threadIdx.x == 0) {
         bad = -1;
@@ -195,8 +138,11 @@ __global__ __launch_bounds__(256) void k_window_reduce(const int64_t* __restrict
     if (m >= 0) atomicMax(&bad, m);
     if (o) atomicOr(&oob, 1);
     __syncthreads();
+    // (dtotal: the total is device-held, `total` bytes for each of *dtotal elements)
     if (threadIdx.x == 0)
-        *result = (idx_err && *idx_err != 0) ? -91 : (oob ? -71 : (bad >= 0 ? wstat[bad] : total));
+        *result = (idx_err && *idx_err != 0)
+                      ? -91
+                      : (oob ? -71 : (bad >= 0 ? wstat[bad] : (dtotal ? *dtotal * total : total)));
 }
 
 }  // namespace
@@ -255,9 +201,9 @@ hipError_t launch_stream_set_status(StreamSetRec* recs, const int64_t* idx_err, 
 }
 
 hipError_t launch_window_reduce(const int64_t* wstat, const WindowTail* wt, int K, const int64_t* idx_err,
-                                int64_t total, int64_t* result, hipStream_t s) {
+                                int64_t total, int64_t* result, hipStream_t s, const int64_t* dtotal) {
     ProfScope prof("k_window_reduce", s);
-    hipLaunchKernelGGL(k_window_reduce, dim3(1), dim3(256), 0, s, wstat, wt, K, idx_err, total, result);
+    hipLaunchKernelGGL(k_window_reduce, dim3(1), dim3(256), 0, s, wstat, wt, K, idx_err, total, dtotal, result);
     return hipGetLastError();
 }
 

@@ -136,6 +136,26 @@ extern "C" void bshuf_hostcheck_window_set_plan(int64_t count, const int64_t* si
     }
 }
 
+// ... and the plan of ragged windows as k_ragged_plan runs it: n (id, count,
+// start) triples with Mw forced.  nstreams < 0: every window in ONE stream of
+// sizes[0] elements (ids unused); else in stream id of a set of nstreams streams
+// of sizes[], an id outside it being refused.  out as above; word 11: the
+// elements the window takes in the packed output (its count, 0 when refused).
+extern "C" void bshuf_hostcheck_ragged_plan(int64_t nstreams, const int64_t* sizes, int64_t bs, int64_t E,
+                                            int64_t max_window, int64_t Mw, const int64_t* ids,
+                                            const int64_t* counts, const int64_t* starts, int64_t n,
+                                            int64_t* out) {
+    for (int64_t i = 0; i < n; i++) {
+        bshuf::WindowPlan w;
+        const bool known = nstreams < 0 || (ids[i] >= 0 && ids[i] < nstreams);
+        const int64_t size = known ? sizes[nstreams < 0 ? 0 : ids[i]] : 0;
+        bshuf::ragged_plan(size, bs, E, max_window, counts[i], starts[i], Mw, !known, w);
+        const int64_t v[12] = {Mw, w.b0, w.nfull, w.last, w.bad, w.clip_lo, w.clip_n, w.tail_lo, w.tail_n,
+                               w.t0, w.t1, w.bad ? 0 : counts[i]};
+        for (int j = 0; j < 12; j++) out[12 * i + j] = v[j];
+    }
+}
+
 // tile_plan.h as the tile decode's host side uses it.  out[3]: rg, G, Mg.
 extern "C" void bshuf_hostcheck_tile_shape(int64_t rows, int64_t cols, int64_t pitch, int64_t bs, int64_t nb,
                                            int64_t* out) {

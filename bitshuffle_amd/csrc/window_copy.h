@@ -1,10 +1,13 @@
 // window_copy.h -- the copy of one window out of its staging area and its
 // stream's verbatim tail, by the window decode of one stream and of a set of
-// streams (k_window_gather, lz4_window.hip).
+// streams (k_window_gather, lz4_window.hip) and by the ragged one
+// (k_ragged_gather, lz4_ragged.hip); and the table entries of one window that
+// their plan kernels write.
 #pragma once
 
 #include "launch.h"
 #include "range_worklist.h"
+#include "window_plan.h"
 
 namespace bshuf {
 
@@ -54,6 +57,64 @@ __device__ __forceinline__ void span_copy(const uint8_t* src, uint8_t* dst, int6
         }
     }
     for (int64_t i = head + 16 * nv + t; i < n; i += T) d8[i] = s8[i];
+}
+
+// Window i's Seg (Mw consecutive blocks of the stream at `in`, decoded back to
+// back into staging area i), its piece (the clip of that area, which goes to
+// dst) and its tail span.
+__device__ __forceinline__ void write_window(const WindowCall& c, int i, const WindowPlan& w, const uint8_t* in,
+                                             uint8_t* dst, Seg* __restrict__ segs, RangePiece* __restrict__ pcs,
+                                             WindowTail* __restrict__ wt) {
+    uint8_t* slot = c.slots + (int64_t)i * c.slot;
+    Seg g;
+    g.in = in;
+    g.out = slot;
+    g.first = (int64_t)i * c.Mw;
+    g.nfull = w.nfull;
+    g.tail = 0;
+    g.in_nbytes = 0;  // the work list: the end of the window's last record
+    g.chunk0 = 0;
+    g.nchunks = 0;
+    g.seq0 = 0;       // the work list
+    g.result = c.res + i;
+    g.last = w.last;
+    g.pad_ = 0;
+    segs[i] = g;
+    RangePiece pc;
+    pc.b0 = w.b0;
+    pc.nblk = c.Mw;
+    pc.seq_base = c.seq_words < 0 ? -1 : (int64_t)i * c.seq_words;
+    pc.src = slot + w.clip_lo;
+    pc.dst = dst;
+    pc.lo = 0;
+    pc.n = w.clip_n;
+    pc.kind = kPieceEdge;
+    pc.pad_ = 0;
+    pcs[i] = pc;
+    WindowTail t;
+    t.lo = w.tail_lo;
+    t.n = w.tail_n;
+    t.t0 = (int32_t)w.t0;
+    t.t1 = (int32_t)w.t1;
+    t.bad = w.bad;
+    t.pad_ = 0;
+    wt[i] = t;
+}
+
+// For the gather: window i's stream and that stream's error word.
+__device__ __forceinline__ RangeStream source_stream(const WindowStream& src, const WindowTail&, int,
+                                                     int64_t& err) {
+    err = 0;
+    return src.st;
+}
+
+__device__ __forceinline__ RangeStream source_stream(const WindowSet& src, const WindowTail& w, int i,
+                                                     int64_t& err) {
+    err = 0;
+    if (w.bad) return RangeStream{};
+    const StreamSetRec r = src.recs[src.sidx[i]];
+    err = r.err;
+    return r.st;
 }
 
 // Window i of a call by lanes t of T; st is the window's stream and err that

@@ -3,7 +3,8 @@
 // One pure function, run per window by k_window_plan on the device (the starts
 // live in device memory) and by the CPU suite through libbshuf_hostcheck.so:
 // no HIP but the qualifiers below.  window_set_plan, at the end, is the same for
-// a window in one of a set of streams (bshuf_decompress_lz4_windows_set_dev).
+// a window in one of a set of streams (bshuf_decompress_lz4_windows_set_dev),
+// ragged_plan for a window with a length of its own (bshuf_decompress_lz4_ragged_dev).
 //
 // The stream of `size` elements in blocks of `bs` (plan.h, make_plan): nfull
 // full blocks, one partial block of `last` elements when that is not 0, then
@@ -116,6 +117,34 @@ BSHUF_WINDOW_FN void window_set_plan(int64_t count, int64_t id, int64_t size, in
         return;
     }
     window_plan_blocks(size, bs, E, window, start, Mw, start < 0 || start > size - window, w);
+}
+
+// ---- ragged windows (bshuf_decompress_lz4_ragged_dev, ..._ragged_set_dev) ----
+// Window i of such a call is elements [start, start + count) of its stream, the
+// count device-held like the start; the host knows an upper bound max_window,
+// and Mw = window_blocks(size of the (largest) stream, bs, max_window) for every
+// window.  The window is good when 0 <= count <= max_window and 0 <= start <=
+// size - count (`size`: its stream's; 0 for a stream the set does not have, so
+// that only count 0 at start 0 could pass -- the caller refuses an unknown id
+// itself).
+BSHUF_WINDOW_FN bool ragged_good(int64_t size, int64_t max_window, int64_t start, int64_t count) {
+    return count >= 0 && count <= max_window && count <= size && start >= 0 && start <= size - count;
+}
+
+// The plan of one ragged window: window_plan_blocks with the window's own count
+// and min(Mw, nb) blocks, nb the blocks of its stream.  A stream with at least
+// Mw blocks gets what a fixed-length window of `count` elements with Mw forced
+// gets: of the Mw work blocks only [t0, t1) hold bytes of the window, and the
+// caller leaves the others inert.  A stream of a set with fewer blocks than Mw
+// plans good all the same: b0 = 0, nfull / last describe its nb blocks, and work
+// blocks [nb, Mw) are inert like the others outside [t0, t1).  refused: the
+// caller's own reasons (unknown stream, no room in the output) on top of
+// ragged_good; a refused window has b0 = 0, t0 = t1 = 0 and nothing to copy.
+BSHUF_WINDOW_FN void ragged_plan(int64_t size, int64_t bs, int64_t E, int64_t max_window, int64_t count,
+                                 int64_t start, int64_t Mw, bool refused, WindowPlan& w) {
+    const int64_t nb = size / bs + (size % bs - size % 8 ? 1 : 0);
+    const bool bad = refused || !ragged_good(size, max_window, start, count);
+    window_plan_blocks(size, bs, E, bad ? 0 : count, start, Mw < nb ? Mw : nb, bad, w);
 }
 
 }  // namespace bshuf

@@ -246,6 +246,76 @@ int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, si
                                              void* out, void* ws, size_t ws_bytes, int64_t* d_result,
                                              int64_t* d_status, void* stream);
 
+/* ---- ragged window decode: device-held starts AND lengths (additive) ----
+ *
+ * Decodes nwindows windows whose lengths differ and live in device memory like
+ * their starts: window i is elements [d_starts[i], d_starts[i] + d_counts[i]) of
+ * ONE framed stream (bshuf_decompress_lz4_ragged_dev; in .. block_size and
+ * block_offsets as for the window entry) or of stream d_ids[i] of a stream set
+ * (bshuf_decompress_lz4_ragged_set_dev; d_set, count, max_size as for the window
+ * entry over a set).  d_starts, d_counts (and d_ids) are DEVICE int64 arrays of
+ * nwindows words that the host never reads.  max_window, a bound on the counts,
+ * nwindows, out_capacity and out_pitch (both in elements) are host values; with
+ * the stream (or count, max_size) they fix the workspace
+ * (bshuf_decompress_lz4_ragged[_set]_dev_workspace(...) bytes, or NULL) and the
+ * launch sequence: one linear chain on `stream`, nothing uploaded, nothing
+ * synchronised, and a call captured into a graph follows the arrays at every
+ * replay.
+ *
+ * Window i is GOOD when 0 <= d_counts[i] <= max_window and 0 <= d_starts[i] <=
+ * size - d_counts[i], size being its stream's element count -- over a set,
+ * d_ids[i] must also name one of its streams, which may have any number of
+ * blocks.  A good window of count 0 has status 0 and writes nothing.  Any other
+ * window is REFUSED: status -71, nothing written.  Over a set whose header does
+ * not carry the call's count, elem_size, block_size and nb_max, every window is
+ * refused and no stream is read.
+ *
+ * Packed output (out_pitch == 0): window i lands at out + off[i] * elem_size,
+ * off being the exclusive scan of eff[i] = d_counts[i] for a good window and 0
+ * for a refused one; off[0 .. nwindows] is written to d_out_offsets (device,
+ * nwindows + 1 words, required): values + offsets, as a jagged tensor has them.
+ * The offsets depend on starts, counts and ids only: a window whose block fails
+ * to decode keeps its room, and its bytes stay untouched.  A good window with
+ * off[i] + d_counts[i] > out_capacity is not written and gets -71 (the offsets
+ * stay the plain scan); nothing is written at or behind out + out_capacity *
+ * elem_size.  Padded output (out_pitch >= max_window): window i lands at out +
+ * i * out_pitch * elem_size, the rest of its row stays untouched, out_capacity
+ * must be at least nwindows * out_pitch, and d_out_offsets may be NULL (given,
+ * it still receives the scan).
+ *
+ * d_status[i] (device, nwindows words, or NULL): d_counts[i] * elem_size; or
+ * -71 for a refused window; or -91 for a stream of a set whose rebuilt index
+ * failed; or the code of the highest failing block among those that hold the
+ * window's elements -- a neighbouring block's failure is not the window's; or
+ * -91 when the window reaches a verbatim tail that is not inside its stream.
+ * *d_result: -91 for a bad rebuilt index, else -71 when any window was refused,
+ * else the status of the highest-numbered failing window, else the bytes
+ * written, off[nwindows] * elem_size.
+ *
+ * Returns 0 once enqueued (nwindows == 0 or max_window == 0: *d_result = 0 and
+ * d_out_offsets, when given, zero-filled).  Host errors: -81; -71 for
+ * max_window > size (max_size), nwindows * ((max_window + block_size - 2) /
+ * block_size + 1) >= 2^31, a block above the LDS decoder's size, 0 < out_pitch <
+ * max_window, out_capacity < nwindows * out_pitch, out_pitch == 0 without
+ * d_out_offsets, a workspace that is too small or not 256-byte aligned, d_set
+ * NULL or not 256-byte aligned; -70 without a device. */
+size_t bshuf_decompress_lz4_ragged_dev_workspace(size_t in_nbytes, size_t size, size_t elem_size,
+                                                 size_t block_size, size_t nwindows, size_t max_window);
+int64_t bshuf_decompress_lz4_ragged_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                        size_t block_size, const int64_t* d_starts, const int64_t* d_counts,
+                                        size_t nwindows, size_t max_window, void* out, size_t out_capacity,
+                                        size_t out_pitch, int64_t* d_out_offsets, void* ws, size_t ws_bytes,
+                                        int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
+                                        void* stream);
+size_t bshuf_decompress_lz4_ragged_set_dev_workspace(size_t max_size, size_t elem_size, size_t block_size,
+                                                     size_t nwindows, size_t max_window);
+int64_t bshuf_decompress_lz4_ragged_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                            size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                            const int64_t* d_counts, size_t nwindows, size_t max_window,
+                                            void* out, size_t out_capacity, size_t out_pitch,
+                                            int64_t* d_out_offsets, void* ws, size_t ws_bytes,
+                                            int64_t* d_result, int64_t* d_status, void* stream);
+
 /* ---- tile decode: rows x cols crops at device-held corners (additive) ----
  *
  * Decodes `ntiles` tiles of rows x cols elements each, of ONE framed stream
