@@ -47,6 +47,15 @@ tensors, bounded by max_window; packed back to back with an offsets tensor
     decompress_lz4_ragged_workspace(in_nbytes, size, elem_size, nwindows, max_window, ...)
     decompress_lz4_ragged_set_dev(sset, dtype, ids, starts, counts, max_window, ...)
     decompress_lz4_ragged_set_workspace(sset, nwindows, max_window, ...)
+Decode to float (device): the six window, tile and ragged functions above take
+    out_dtype=None, scale=1.0, offset=0.0
+With out_dtype torch.float32, float16 or bfloat16 every element x of the stream
+(dtype uint8, int8, uint16, int16, uint32, int32 or float32) lands as
+out_dtype(fmaf(float32(x), scale, offset)) -- one fp32 fused multiply-add, every
+rounding to nearest even -- written by the kernel that copies the decoded
+elements out (bshuf_decompress_lz4_*_cvt_dev).  `out` has out_dtype and the usual
+shape; status and result go on counting the stream's bytes; the workspaces are
+the plain calls'.  out_dtype=None: nothing changes.
 """
 from ._lib import (  # noqa: F401
     LIB_PATH,

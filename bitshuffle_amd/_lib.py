@@ -68,6 +68,19 @@ PROTOTYPES = {
     "bshuf_decompress_lz4_tiles_set_dev_workspace": (_sz, [_sz, _sz, _sz, _sz, _sz, _sz, _sz]),
     "bshuf_decompress_lz4_tiles_set_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _sz, _vp,
                                                   _vp, _sz, _vp, _vp, _vp]),
+    # ... and their converting twins: the same arguments and a bshuf_cvt*
+    "bshuf_decompress_lz4_windows_cvt_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz,
+                                                    _vp, _vp, _vp, _vp, _vp]),
+    "bshuf_decompress_lz4_windows_set_cvt_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _vp,
+                                                        _sz, _vp, _vp, _vp, _vp]),
+    "bshuf_decompress_lz4_ragged_cvt_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _sz, _sz,
+                                                   _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "bshuf_decompress_lz4_ragged_set_cvt_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _sz, _sz, _vp,
+                                                       _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "bshuf_decompress_lz4_tiles_cvt_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _vp,
+                                                  _sz, _vp, _vp, _vp, _vp, _vp]),
+    "bshuf_decompress_lz4_tiles_set_cvt_dev": (_i64, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _sz, _sz, _vp,
+                                                      _vp, _sz, _vp, _vp, _vp, _vp]),
     "bshuf_lz4_fast_version": (_int, []),
     "bshuf_compress_lz4_fast": (_i64, [_vp, _vp, _sz, _sz, _sz]),
     "bshuf_compress_lz4_fast_dev": (_i64, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
@@ -97,6 +110,17 @@ PROTOTYPES = {
        for f in fs},
     "bshuf_host_xfer_stats": (None, [_vp]),
 }
+
+
+class Cvt(ctypes.Structure):
+    """bshuf_cvt of include/bitshuffle.h."""
+    _fields_ = [("src", ctypes.c_int32), ("dst", ctypes.c_int32), ("scale", ctypes.c_float),
+                ("offset", ctypes.c_float)]
+
+
+# BSHUF_CVT_* source and destination kinds, by name
+CVT_SRC = {"uint8": 0, "int8": 1, "uint16": 2, "int16": 3, "uint32": 4, "int32": 5, "float32": 6}
+CVT_DST = {"float32": 0, "float16": 1, "bfloat16": 2}
 
 
 class BshufError(RuntimeError):

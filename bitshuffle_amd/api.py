@@ -14,7 +14,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import BshufError, lib
+from ._lib import CVT_DST, CVT_SRC, BshufError, Cvt, lib
 
 
 def _fail(code, what="Failed. Error code %d."):
@@ -329,14 +329,46 @@ def decompress_lz4_range_dev(buf, size, dtype, start, count, **kw):
     return r if kw.get("sync", True) is False else r[0]
 
 
+def _dtype_name(dtype):
+    torch = _torch()
+    return str(dtype).split(".")[-1] if isinstance(dtype, torch.dtype) else np.dtype(dtype).name
+
+
+def _cvt(dtype, out_dtype, scale, offset, elem_size):
+    """The bshuf_cvt of a converting call (out_dtype given), else None: `dtype`
+    names the stream's elements, `out_dtype` those of `out`."""
+    if out_dtype is None:
+        return None
+    if elem_size is not None:
+        raise ValueError("out_dtype converts elements of `dtype`: it does not go with elem_size=")
+    src, dst = CVT_SRC.get(_dtype_name(dtype)), CVT_DST.get(_dtype_name(out_dtype))
+    if dst is None:
+        raise ValueError("out_dtype must be torch.float32, float16 or bfloat16, not %s" % (out_dtype,))
+    if src is None:
+        raise ValueError("out_dtype needs a dtype of uint8, int8, uint16, int16, uint32, int32 or float32, not %s"
+                         % (dtype,))
+    return Cvt(src, dst, float(scale), float(offset))
+
+
+def _cvt_out(cvt, out, out_dtype):
+    """A converting call's `out`: of out_dtype, aligned to it.  Returns the
+    stream's element size."""
+    if out.dtype != out_dtype:
+        raise ValueError("out must be a %s tensor, not %s" % (out_dtype, out.dtype))
+    if out.data_ptr() % out.element_size():
+        raise ValueError("out must be aligned to its %d-byte elements" % out.element_size())
+    return 1 if cvt.src < 2 else 2 if cvt.src < 4 else 4
+
+
 def _windows_dev(call, device, whose, index, dtype, window, out, workspace, result, status, sync, elem_size,
-                 holds=None):
+                 holds=None, cvt=None, out_dtype=None):
     """What the window decodes of one stream and of a set share.  `index`:
     (name, tensor) pairs, the device tensors with one entry per window each;
     `device`: where they must live, called the "`whose` device" in messages.
     `holds`: the element size the set was built with.  call(es, K, window, out,
     ws, ws_bytes, result, status) makes the library call with these arguments
-    of its own among the others and returns its code."""
+    of its own among the others and returns its code.  cvt, out_dtype: a
+    converting call (_cvt): `out` is of out_dtype, sized in its elements."""
     torch = _torch()
     for name, t in index:
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
@@ -350,16 +382,22 @@ def _windows_dev(call, device, whose, index, dtype, window, out, workspace, resu
     if window < 0:
         raise ValueError("window must be >= 0, not %d" % window)
     if out is None:
-        if elem_size is None:
+        if cvt is not None:
+            out = torch.empty((K, window), dtype=out_dtype, device=device)
+        elif elem_size is None:
             out = torch.empty((K, window), dtype=dtype, device=device)
         else:
             out = torch.empty((K, window * int(elem_size)), dtype=torch.uint8, device=device)
-    es = out.element_size() if elem_size is None else int(elem_size)
+    if cvt is not None:
+        es = _cvt_out(cvt, out, out_dtype)
+    else:
+        es = out.element_size() if elem_size is None else int(elem_size)
     if holds is not None and es != holds:
         raise ValueError("the set holds %d-byte elements, not %d-byte ones" % (holds, es))
-    if out.numel() * out.element_size() < K * window * es:
+    per = out.element_size() if cvt is not None else es  # bytes of `out` per element
+    if out.numel() * out.element_size() < K * window * per:
         raise ValueError("out holds %d bytes, the windows need %d"
-                         % (out.numel() * out.element_size(), K * window * es))
+                         % (out.numel() * out.element_size(), K * window * per))
     if status is not None and (status.dtype != torch.int64 or status.numel() < K):
         raise ValueError("status must be an int64 tensor of %d entries" % K)
     if result is None:
@@ -389,7 +427,7 @@ def decompress_lz4_windows_workspace(in_nbytes, size, elem_size, nwindows, windo
 
 def decompress_lz4_windows_dev(buf, size, dtype, starts, window, block_size=0, out=None,
                                workspace=None, result=None, status=None, offsets=None, stream=None,
-                               sync=True, elem_size=None):
+                               sync=True, elem_size=None, out_dtype=None, scale=1.0, offset=0.0):
     """Window decode (bshuf_decompress_lz4_windows_dev): K = starts.numel()
     windows of `window` elements each of the framed stream in uint8 device
     tensor `buf`, which encodes `size` elements of `dtype`.  `starts` is a
@@ -402,13 +440,26 @@ def decompress_lz4_windows_dev(buf, size, dtype, starts, window, block_size=0, o
     K entries): per window its byte count, -71 for a start outside [0, size -
     window] (that window's part of `out` is left as it was), or the code of a
     failing block it touches.  `offsets`: the stream's block index; without it
-    the index is rebuilt from the whole stream."""
+    the index is rebuilt from the whole stream.
+
+    Decode to float (bshuf_decompress_lz4_windows_cvt_dev): with `out_dtype`
+    torch.float32, float16 or bfloat16 the (K, window) result is of that dtype
+    and every element x lands as out_dtype(fmaf(float32(x), scale, offset)), one
+    fp32 fused multiply-add, every rounding to nearest even; `dtype` is then
+    uint8, int8, uint16, int16, uint32, int32 or float32 (ValueError otherwise,
+    and with elem_size=), a caller's `out` is of out_dtype, and `status` and
+    `result` go on counting the stream's bytes."""
+    cvt = _cvt(dtype, out_dtype, scale, offset, elem_size)
+
     def call(es, K, window, *ptrs):
         offp = _dptr(offsets) if offsets is not None else None
-        return lib.bshuf_decompress_lz4_windows_dev(_dptr(buf), buf.numel(), int(size), es, block_size,
-                                                    _dptr(starts), K, window, *ptrs, offp, _stream(stream))
+        args = (_dptr(buf), buf.numel(), int(size), es, block_size, _dptr(starts), K, window, *ptrs, offp,
+                _stream(stream))
+        if cvt is not None:
+            return lib.bshuf_decompress_lz4_windows_cvt_dev(*args, ctypes.byref(cvt))
+        return lib.bshuf_decompress_lz4_windows_dev(*args)
     return _windows_dev(call, buf.device, "stream's", [("starts", starts)], dtype, window, out, workspace,
-                        result, status, sync, elem_size)
+                        result, status, sync, elem_size, cvt=cvt, out_dtype=out_dtype)
 
 
 class StreamSet:
@@ -479,7 +530,8 @@ def decompress_lz4_windows_set_workspace(sset, nwindows, window, device=None):
 
 
 def decompress_lz4_windows_set_dev(sset, dtype, ids, starts, window, out=None, workspace=None, result=None,
-                                   status=None, stream=None, sync=True, elem_size=None):
+                                   status=None, stream=None, sync=True, elem_size=None, out_dtype=None,
+                                   scale=1.0, offset=0.0):
     """Window decode over a StreamSet (bshuf_decompress_lz4_windows_set_dev):
     window i is elements [starts[i], starts[i] + window) of stream ids[i].
     `ids` and `starts` are contiguous int64 DEVICE tensors of equal length K,
@@ -492,17 +544,24 @@ def decompress_lz4_windows_set_dev(sset, dtype, ids, starts, window, out=None, w
     or a stream of fewer than min((window + block_size - 2) // block_size + 1,
     blocks of the largest stream) blocks (that window's part of `out` is left as
     it was); -91 for a stream whose rebuilt index failed; or the code of a
-    failing block the window touches."""
+    failing block the window touches.  `out_dtype`, `scale`, `offset`: decode
+    to float, as decompress_lz4_windows_dev
+    (bshuf_decompress_lz4_windows_set_cvt_dev)."""
+    cvt = _cvt(dtype, out_dtype, scale, offset, elem_size)
+
     def call(es, K, window, *ptrs):
-        return lib.bshuf_decompress_lz4_windows_set_dev(_dptr(sset.table), sset.count, sset.max_size, es,
-                                                        sset.block_size, _dptr(ids), _dptr(starts), K, window,
-                                                        *ptrs, _stream(stream))
+        args = (_dptr(sset.table), sset.count, sset.max_size, es, sset.block_size, _dptr(ids), _dptr(starts), K,
+                window, *ptrs, _stream(stream))
+        if cvt is not None:
+            return lib.bshuf_decompress_lz4_windows_set_cvt_dev(*args, ctypes.byref(cvt))
+        return lib.bshuf_decompress_lz4_windows_set_dev(*args)
     return _windows_dev(call, sset.device, "set's", [("ids", ids), ("starts", starts)], dtype, window, out,
-                        workspace, result, status, sync, elem_size, holds=sset.elem_size)
+                        workspace, result, status, sync, elem_size, holds=sset.elem_size, cvt=cvt,
+                        out_dtype=out_dtype)
 
 
 def _ragged_dev(call, device, whose, index, dtype, max_window, out, out_offsets, pitch, workspace, result,
-                status, sync, elem_size, holds=None):
+                status, sync, elem_size, holds=None, cvt=None, out_dtype=None):
     """What the ragged decodes of one stream and of a set share, as _windows_dev
     for the window decodes.  call(es, K, max_window, out, capacity, pitch,
     out_offsets, ws, ws_bytes, result, status) makes the library call."""
@@ -521,11 +580,17 @@ def _ragged_dev(call, device, whose, index, dtype, max_window, out, out_offsets,
     per = 1 if elem_size is None else int(elem_size)  # out items per element
     if out is None:
         shape = (K, pitch * per) if pitch else (K * max_window * per,)
-        out = torch.empty(shape, dtype=dtype if elem_size is None else torch.uint8, device=device)
-    es = out.element_size() if elem_size is None else int(elem_size)
+        own = out_dtype if cvt is not None else dtype if elem_size is None else torch.uint8
+        out = torch.empty(shape, dtype=own, device=device)
+    if cvt is not None:
+        es = _cvt_out(cvt, out, out_dtype)
+    else:
+        es = out.element_size() if elem_size is None else int(elem_size)
     if holds is not None and es != holds:
         raise ValueError("the set holds %d-byte elements, not %d-byte ones" % (holds, es))
-    capacity = out.numel() * out.element_size() // es
+    capacity = out.numel() if cvt is not None else out.numel() * out.element_size() // es
+    if cvt is not None and pitch and capacity < K * pitch:
+        raise ValueError("out holds %d elements, %d rows of %d need %d" % (capacity, K, pitch, K * pitch))
     if out_offsets is None:
         out_offsets = torch.empty(K + 1, dtype=torch.int64, device=device)
     if out_offsets.dtype != torch.int64 or out_offsets.numel() < K + 1 or not out_offsets.is_contiguous():
@@ -561,7 +626,7 @@ def decompress_lz4_ragged_workspace(in_nbytes, size, elem_size, nwindows, max_wi
 
 def decompress_lz4_ragged_dev(buf, size, dtype, starts, counts, max_window, out=None, out_offsets=None,
                               pitch=0, block_size=0, workspace=None, result=None, status=None, offsets=None,
-                              stream=None, sync=True, elem_size=None):
+                              stream=None, sync=True, elem_size=None, out_dtype=None, scale=1.0, offset=0.0):
     """Ragged window decode (bshuf_decompress_lz4_ragged_dev): window i is
     elements [starts[i], starts[i] + counts[i]) of the framed stream in uint8
     device tensor `buf`, which encodes `size` elements of `dtype`.  `starts` and
@@ -579,14 +644,23 @@ def decompress_lz4_ragged_dev(buf, size, dtype, starts, counts, max_window, out=
     `result`), or (out, out_offsets, status, result) (sync=False).  `status`
     (int64 device tensor, K entries): per window its byte count, -71, or the
     code of a failing block that holds elements of it.  `offsets`: the stream's
-    block index; without it the index is rebuilt from the whole stream."""
+    block index; without it the index is rebuilt from the whole stream.
+    `out_dtype`, `scale`, `offset`: decode to float, as
+    decompress_lz4_windows_dev (bshuf_decompress_lz4_ragged_cvt_dev); `out`,
+    its capacity, `pitch` and `out_offsets` then count elements of out_dtype,
+    `status` and `result` the stream's bytes."""
+    cvt = _cvt(dtype, out_dtype, scale, offset, elem_size)
+
     def call(es, K, max_window, outp, capacity, pitch, *ptrs):
         offp = _dptr(offsets) if offsets is not None else None
-        return lib.bshuf_decompress_lz4_ragged_dev(_dptr(buf), buf.numel(), int(size), es, block_size,
-                                                   _dptr(starts), _dptr(counts), K, max_window, outp, capacity,
-                                                   pitch, *ptrs, offp, _stream(stream))
+        args = (_dptr(buf), buf.numel(), int(size), es, block_size, _dptr(starts), _dptr(counts), K, max_window,
+                outp, capacity, pitch, *ptrs, offp, _stream(stream))
+        if cvt is not None:
+            return lib.bshuf_decompress_lz4_ragged_cvt_dev(*args, ctypes.byref(cvt))
+        return lib.bshuf_decompress_lz4_ragged_dev(*args)
     return _ragged_dev(call, buf.device, "stream's", [("starts", starts), ("counts", counts)], dtype,
-                       max_window, out, out_offsets, pitch, workspace, result, status, sync, elem_size)
+                       max_window, out, out_offsets, pitch, workspace, result, status, sync, elem_size, cvt=cvt,
+                       out_dtype=out_dtype)
 
 
 def decompress_lz4_ragged_set_workspace(sset, nwindows, max_window, device=None):
@@ -600,24 +674,29 @@ def decompress_lz4_ragged_set_workspace(sset, nwindows, max_window, device=None)
 
 def decompress_lz4_ragged_set_dev(sset, dtype, ids, starts, counts, max_window, out=None, out_offsets=None,
                                   pitch=0, workspace=None, result=None, status=None, stream=None, sync=True,
-                                  elem_size=None):
+                                  elem_size=None, out_dtype=None, scale=1.0, offset=0.0):
     """Ragged window decode over a StreamSet (bshuf_decompress_lz4_ragged_set_dev):
     window i is elements [starts[i], starts[i] + counts[i]) of stream ids[i];
     everything else as decompress_lz4_ragged_dev.  An id outside the set refuses
     the window (-71); a stream of any number of blocks takes windows, also one
-    with fewer blocks than a window of max_window elements may touch."""
+    with fewer blocks than a window of max_window elements may touch.
+    `out_dtype`, `scale`, `offset`: decode to float
+    (bshuf_decompress_lz4_ragged_set_cvt_dev)."""
+    cvt = _cvt(dtype, out_dtype, scale, offset, elem_size)
+
     def call(es, K, max_window, outp, capacity, pitch, *ptrs):
-        return lib.bshuf_decompress_lz4_ragged_set_dev(_dptr(sset.table), sset.count, sset.max_size, es,
-                                                       sset.block_size, _dptr(ids), _dptr(starts),
-                                                       _dptr(counts), K, max_window, outp, capacity, pitch,
-                                                       *ptrs, _stream(stream))
+        args = (_dptr(sset.table), sset.count, sset.max_size, es, sset.block_size, _dptr(ids), _dptr(starts),
+                _dptr(counts), K, max_window, outp, capacity, pitch, *ptrs, _stream(stream))
+        if cvt is not None:
+            return lib.bshuf_decompress_lz4_ragged_set_cvt_dev(*args, ctypes.byref(cvt))
+        return lib.bshuf_decompress_lz4_ragged_set_dev(*args)
     return _ragged_dev(call, sset.device, "set's", [("ids", ids), ("starts", starts), ("counts", counts)],
                        dtype, max_window, out, out_offsets, pitch, workspace, result, status, sync, elem_size,
-                       holds=sset.elem_size)
+                       holds=sset.elem_size, cvt=cvt, out_dtype=out_dtype)
 
 
 def _tiles_dev(call, device, whose, index, dtype, rows, cols, pitch, out, workspace, result, status, sync,
-               elem_size, holds=None):
+               elem_size, holds=None, cvt=None, out_dtype=None):
     """What the tile decodes of one stream and of a set share, as _windows_dev
     for the window decodes.  `index`: (name, tensor) pairs, the device tensors
     with one entry per tile each.  call(es, K, rows, cols, pitch, out, ws,
@@ -637,16 +716,22 @@ def _tiles_dev(call, device, whose, index, dtype, rows, cols, pitch, out, worksp
         if v < 0:
             raise ValueError("%s must be >= 0, not %d" % (name, v))
     if out is None:
-        if elem_size is None:
+        if cvt is not None:
+            out = torch.empty((K, rows, cols), dtype=out_dtype, device=device)
+        elif elem_size is None:
             out = torch.empty((K, rows, cols), dtype=dtype, device=device)
         else:
             out = torch.empty((K, rows, cols * int(elem_size)), dtype=torch.uint8, device=device)
-    es = out.element_size() if elem_size is None else int(elem_size)
+    if cvt is not None:
+        es = _cvt_out(cvt, out, out_dtype)
+    else:
+        es = out.element_size() if elem_size is None else int(elem_size)
     if holds is not None and es != holds:
         raise ValueError("the set holds %d-byte elements, not %d-byte ones" % (holds, es))
-    if out.numel() * out.element_size() < K * rows * cols * es:
+    per = out.element_size() if cvt is not None else es  # bytes of `out` per element
+    if out.numel() * out.element_size() < K * rows * cols * per:
         raise ValueError("out holds %d bytes, the tiles need %d"
-                         % (out.numel() * out.element_size(), K * rows * cols * es))
+                         % (out.numel() * out.element_size(), K * rows * cols * per))
     if status is not None and (status.dtype != torch.int64 or status.numel() < K):
         raise ValueError("status must be an int64 tensor of %d entries" % K)
     if result is None:
@@ -676,7 +761,7 @@ def decompress_lz4_tiles_workspace(in_nbytes, size, elem_size, ntiles, rows, col
 
 def decompress_lz4_tiles_dev(buf, size, dtype, starts, rows, cols, pitch, block_size=0, out=None,
                              workspace=None, result=None, status=None, offsets=None, stream=None,
-                             sync=True, elem_size=None):
+                             sync=True, elem_size=None, out_dtype=None, scale=1.0, offset=0.0):
     """Tile decode (bshuf_decompress_lz4_tiles_dev): K = starts.numel() tiles of
     rows x cols elements each of the framed stream in uint8 device tensor `buf`,
     which encodes `size` elements of `dtype`.  Row r of tile i is elements
@@ -692,14 +777,21 @@ def decompress_lz4_tiles_dev(buf, size, dtype, starts, rows, cols, pitch, block_
     outside [0, size - ((rows - 1) * pitch + cols)], or the code of a failing
     block that holds one of its elements; a tile with a negative status is left
     as it was in `out`, all of it.  `offsets`: the stream's block index; without
-    it the index is rebuilt from the whole stream."""
+    it the index is rebuilt from the whole stream.  `out_dtype`, `scale`,
+    `offset`: decode to float, as decompress_lz4_windows_dev
+    (bshuf_decompress_lz4_tiles_cvt_dev): a (K, rows, cols) tensor of
+    out_dtype."""
+    cvt = _cvt(dtype, out_dtype, scale, offset, elem_size)
+
     def call(es, K, rows, cols, pitch, *ptrs):
         offp = _dptr(offsets) if offsets is not None else None
-        return lib.bshuf_decompress_lz4_tiles_dev(_dptr(buf), buf.numel(), int(size), es, block_size,
-                                                  _dptr(starts), K, rows, cols, pitch, *ptrs, offp,
-                                                  _stream(stream))
+        args = (_dptr(buf), buf.numel(), int(size), es, block_size, _dptr(starts), K, rows, cols, pitch, *ptrs,
+                offp, _stream(stream))
+        if cvt is not None:
+            return lib.bshuf_decompress_lz4_tiles_cvt_dev(*args, ctypes.byref(cvt))
+        return lib.bshuf_decompress_lz4_tiles_dev(*args)
     return _tiles_dev(call, buf.device, "stream's", [("starts", starts)], dtype, rows, cols, pitch, out,
-                      workspace, result, status, sync, elem_size)
+                      workspace, result, status, sync, elem_size, cvt=cvt, out_dtype=out_dtype)
 
 
 def decompress_lz4_tiles_set_workspace(sset, ntiles, rows, cols, pitch, device=None):
@@ -713,7 +805,8 @@ def decompress_lz4_tiles_set_workspace(sset, ntiles, rows, cols, pitch, device=N
 
 
 def decompress_lz4_tiles_set_dev(sset, dtype, ids, starts, rows, cols, pitch, out=None, workspace=None,
-                                 result=None, status=None, stream=None, sync=True, elem_size=None):
+                                 result=None, status=None, stream=None, sync=True, elem_size=None,
+                                 out_dtype=None, scale=1.0, offset=0.0):
     """Tile decode over a StreamSet (bshuf_decompress_lz4_tiles_set_dev): row r
     of tile i is elements [starts[i] + r * pitch, ... + cols) of stream ids[i] --
     a rows x cols crop of frame ids[i] of a stack of images stored one stream
@@ -728,13 +821,19 @@ def decompress_lz4_tiles_set_dev(sset, dtype, ids, starts, rows, cols, pitch, ou
     fewer blocks than a group of the tile's rows decodes (that tile's part of
     `out` is left as it was); -91 for a stream whose rebuilt index failed; or
     the code of a failing block that holds one of the tile's elements, and then
-    none of the tile is written."""
+    none of the tile is written.  `out_dtype`, `scale`, `offset`: decode to
+    float (bshuf_decompress_lz4_tiles_set_cvt_dev)."""
+    cvt = _cvt(dtype, out_dtype, scale, offset, elem_size)
+
     def call(es, K, rows, cols, pitch, *ptrs):
-        return lib.bshuf_decompress_lz4_tiles_set_dev(_dptr(sset.table), sset.count, sset.max_size, es,
-                                                      sset.block_size, _dptr(ids), _dptr(starts), K, rows, cols,
-                                                      pitch, *ptrs, _stream(stream))
+        args = (_dptr(sset.table), sset.count, sset.max_size, es, sset.block_size, _dptr(ids), _dptr(starts), K,
+                rows, cols, pitch, *ptrs, _stream(stream))
+        if cvt is not None:
+            return lib.bshuf_decompress_lz4_tiles_set_cvt_dev(*args, ctypes.byref(cvt))
+        return lib.bshuf_decompress_lz4_tiles_set_dev(*args)
     return _tiles_dev(call, sset.device, "set's", [("ids", ids), ("starts", starts)], dtype, rows, cols, pitch,
-                      out, workspace, result, status, sync, elem_size, holds=sset.elem_size)
+                      out, workspace, result, status, sync, elem_size, holds=sset.elem_size, cvt=cvt,
+                      out_dtype=out_dtype)
 
 
 def block_index_dev(buf, size, elem_size, block_size=0, workspace=None, stream=None):

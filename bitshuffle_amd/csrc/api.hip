@@ -942,6 +942,20 @@ int64_t bshuf_decompress_lz4_ranges_dev(const void* in, size_t in_nbytes, size_t
 
 namespace {
 
+// A converting call's bshuf_cvt (launch.h, "converting gathers"): -71 without
+// one, for a kind that is not one, for a source kind that is not elem_size
+// bytes (so for every elem_size but 1, 2 and 4) and for an `out` that is not
+// aligned to the destination's element.
+int64_t cvt_check(const bshuf_cvt* cvt, size_t elem_size, const void* out, CvtArgs& a) {
+    if (!cvt) return kErrUnsupported;
+    if (cvt->src < 0 || cvt->src >= kCvtSrcKinds || cvt->dst < 0 || cvt->dst >= kCvtDstKinds)
+        return kErrUnsupported;
+    if ((size_t)cvt_src_size(cvt->src) != elem_size) return kErrUnsupported;
+    if ((uintptr_t)out % (size_t)cvt_dst_size(cvt->dst)) return kErrUnsupported;
+    a = CvtArgs{cvt->src, cvt->dst, cvt->scale, cvt->offset};
+    return 0;
+}
+
 // What the host knows of a window call, over one stream or over a set:
 // everything but the starts (and the stream indices).
 struct WindowShape {
@@ -1028,7 +1042,8 @@ size_t window_ws(const Plan& p, const WindowShape& w, int64_t blocks_end, Window
 extern "C++" template <class MakeSource, class Worklist>
 int64_t window_decode(const Plan& p, const WindowShape& w, int64_t blocks_end, size_t need,
                       const int64_t* d_starts, void* out, void* ws, size_t ws_bytes, int64_t* d_result,
-                      int64_t* d_status, hipStream_t s, MakeSource make_source, Worklist worklist) {
+                      int64_t* d_status, hipStream_t s, const CvtArgs* cvt, MakeSource make_source,
+                      Worklist worklist) {
     DevBuf own;
     const int64_t r = get_ws(ws, ws_bytes, need, own, s);
     if (r) return r;
@@ -1064,7 +1079,7 @@ int64_t window_decode(const Plan& p, const WindowShape& w, int64_t blocks_end, s
             launch_decode_batch(b.segs, nullptr, K, b.blk_seg, L, b.d, s) != hipSuccess)
             return kErrHip;
     }
-    if (launch_window_gather(src, c, b.pcs, b.wt, b.d.status, wstat, s) != hipSuccess ||
+    if (launch_window_gather(src, c, b.pcs, b.wt, b.d.status, wstat, s, cvt) != hipSuccess ||
         launch_window_reduce(wstat, b.wt, K, idx_err, w.K * c.wbytes, d_result, s) != hipSuccess)
         return kErrHip;
     return 0;
@@ -1082,11 +1097,12 @@ size_t bshuf_decompress_lz4_windows_dev_workspace(size_t in_nbytes, size_t size,
     return window_ws(p, w, cb > 0 ? cb : 0, nullptr, nullptr);
 }
 
-int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
-                                         size_t block_size, const int64_t* d_starts, size_t nwindows,
-                                         size_t window, void* out, void* ws, size_t ws_bytes,
-                                         int64_t* d_result, int64_t* d_status,
-                                         const uint64_t* block_offsets, void* stream) {
+namespace {
+// The entry and its converting twin (cvt: checked, or nullptr).
+int64_t windows_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size, size_t block_size,
+                    const int64_t* d_starts, size_t nwindows, size_t window, void* out, void* ws,
+                    size_t ws_bytes, int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
+                    void* stream, const CvtArgs* cvt) {
     Plan p;
     int64_t r = make_plan(size, elem_size, block_size, p);
     if (r) return r;
@@ -1102,7 +1118,7 @@ int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_
     if (nwindows == 0 || window == 0) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
     const uint8_t* i8 = (const uint8_t*)in;
     return window_decode(
-        p, w, cb, need, d_starts, out, ws, ws_bytes, d_result, d_status, s,
+        p, w, cb, need, d_starts, out, ws, ws_bytes, d_result, d_status, s, cvt,
         // the plan reads the stream's address and size only: the index comes behind it
         [&](const WindowBufs&) { return WindowStream{RangeStream{i8}, (int64_t)size}; },
         [&](WindowStream& src, const WindowCall& c, const WindowBufs& b, const int64_t*& idx_err) {
@@ -1112,6 +1128,29 @@ int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_
             if (e != hipSuccess) return e;
             return launch_range_worklist(src.st, b.segs, b.pcs, c.K, c.K, 0, c.Mw, b.d.offs, s);
         });
+}
+}  // namespace
+
+int64_t bshuf_decompress_lz4_windows_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                         size_t block_size, const int64_t* d_starts, size_t nwindows,
+                                         size_t window, void* out, void* ws, size_t ws_bytes,
+                                         int64_t* d_result, int64_t* d_status,
+                                         const uint64_t* block_offsets, void* stream) {
+    return windows_dev(in, in_nbytes, size, elem_size, block_size, d_starts, nwindows, window, out, ws, ws_bytes,
+                       d_result, d_status, block_offsets, stream, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_windows_cvt_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                             size_t block_size, const int64_t* d_starts, size_t nwindows,
+                                             size_t window, void* out, void* ws, size_t ws_bytes,
+                                             int64_t* d_result, int64_t* d_status,
+                                             const uint64_t* block_offsets, void* stream,
+                                             const bshuf_cvt* cvt) {
+    CvtArgs a;
+    const int64_t r = cvt_check(cvt, elem_size, out, a);
+    if (r) return r;
+    return windows_dev(in, in_nbytes, size, elem_size, block_size, d_starts, nwindows, window, out, ws, ws_bytes,
+                       d_result, d_status, block_offsets, stream, &a);
 }
 
 // ---------------------------------------------------------------------------
@@ -1282,11 +1321,11 @@ size_t bshuf_decompress_lz4_windows_set_dev_workspace(size_t max_size, size_t el
     return window_ws(p, w, 0, nullptr, nullptr);
 }
 
-int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
-                                             size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
-                                             size_t nwindows, size_t window, void* out, void* ws,
-                                             size_t ws_bytes, int64_t* d_result, int64_t* d_status,
-                                             void* stream) {
+namespace {
+int64_t windows_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size, size_t block_size,
+                        const int64_t* d_ids, const int64_t* d_starts, size_t nwindows, size_t window, void* out,
+                        void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status, void* stream,
+                        const CvtArgs* cvt) {
     Plan p;
     int64_t r = make_plan(max_size, elem_size, block_size, p);
     if (r) return r;
@@ -1301,7 +1340,7 @@ int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, si
     hipStream_t s = (hipStream_t)stream;
     if (nwindows == 0 || window == 0) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
     return window_decode(
-        p, w, 0, need, d_starts, out, ws, ws_bytes, d_result, d_status, s,
+        p, w, 0, need, d_starts, out, ws, ws_bytes, d_result, d_status, s, cvt,
         [&](const WindowBufs& b) {
             return WindowSet{(const StreamSetHeader*)d_set,
                              (const StreamSetRec*)((const uint8_t*)d_set + kStreamSetRecs),
@@ -1317,6 +1356,28 @@ int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, si
             if (e != hipSuccess) return e;
             return launch_window_set_worklist(src, c, b.segs, b.pcs, b.d.offs, s);
         });
+}
+}  // namespace
+
+int64_t bshuf_decompress_lz4_windows_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                             size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                             size_t nwindows, size_t window, void* out, void* ws,
+                                             size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                             void* stream) {
+    return windows_set_dev(d_set, count, max_size, elem_size, block_size, d_ids, d_starts, nwindows, window, out,
+                           ws, ws_bytes, d_result, d_status, stream, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_windows_set_cvt_dev(const void* d_set, size_t count, size_t max_size,
+                                                 size_t elem_size, size_t block_size, const int64_t* d_ids,
+                                                 const int64_t* d_starts, size_t nwindows, size_t window,
+                                                 void* out, void* ws, size_t ws_bytes, int64_t* d_result,
+                                                 int64_t* d_status, void* stream, const bshuf_cvt* cvt) {
+    CvtArgs a;
+    const int64_t r = cvt_check(cvt, elem_size, out, a);
+    if (r) return r;
+    return windows_set_dev(d_set, count, max_size, elem_size, block_size, d_ids, d_starts, nwindows, window, out,
+                           ws, ws_bytes, d_result, d_status, stream, &a);
 }
 
 // ---------------------------------------------------------------------------
@@ -1370,7 +1431,8 @@ extern "C++" template <class MakeSource, class Index>
 int64_t ragged_decode(const Plan& p, const WindowShape& w, int64_t blocks_end, size_t need,
                       const int64_t* d_starts, const int64_t* d_counts, void* out, size_t out_capacity,
                       size_t out_pitch, int64_t* d_out_offsets, void* ws, size_t ws_bytes, int64_t* d_result,
-                      int64_t* d_status, hipStream_t s, MakeSource make_source, Index index) {
+                      int64_t* d_status, hipStream_t s, const CvtArgs* cvt, MakeSource make_source,
+                      Index index) {
     DevBuf own;
     const int64_t r = get_ws(ws, ws_bytes, need, own, s);
     if (r) return r;
@@ -1414,7 +1476,7 @@ int64_t ragged_decode(const Plan& p, const WindowShape& w, int64_t blocks_end, s
             launch_decode_batch(b.segs, nullptr, K, b.blk_seg, L, b.d, s) != hipSuccess)
             return kErrHip;
     }
-    if (launch_ragged_gather(src, c, b.pcs, b.wt, b.d.status, wstat, s) != hipSuccess ||
+    if (launch_ragged_gather(src, c, b.pcs, b.wt, b.d.status, wstat, s, cvt) != hipSuccess ||
         launch_window_reduce(wstat, b.wt, K, idx_err, p.L.E, d_result, s, c.offs + K) != hipSuccess)
         return kErrHip;
     return 0;
@@ -1433,12 +1495,12 @@ size_t bshuf_decompress_lz4_ragged_dev_workspace(size_t in_nbytes, size_t size, 
     return ragged_ws(p, w, cb > 0 ? cb : 0, nullptr, nullptr);
 }
 
-int64_t bshuf_decompress_lz4_ragged_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
-                                        size_t block_size, const int64_t* d_starts, const int64_t* d_counts,
-                                        size_t nwindows, size_t max_window, void* out, size_t out_capacity,
-                                        size_t out_pitch, int64_t* d_out_offsets, void* ws, size_t ws_bytes,
-                                        int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
-                                        void* stream) {
+namespace {
+int64_t ragged_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size, size_t block_size,
+                   const int64_t* d_starts, const int64_t* d_counts, size_t nwindows, size_t max_window, void* out,
+                   size_t out_capacity, size_t out_pitch, int64_t* d_out_offsets, void* ws, size_t ws_bytes,
+                   int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets, void* stream,
+                   const CvtArgs* cvt) {
     Plan p;
     int64_t r = make_plan(size, elem_size, block_size, p);
     if (r) return r;
@@ -1457,12 +1519,38 @@ int64_t bshuf_decompress_lz4_ragged_dev(const void* in, size_t in_nbytes, size_t
     const uint8_t* i8 = (const uint8_t*)in;
     return ragged_decode(
         p, w, cb, need, d_starts, d_counts, out, out_capacity, out_pitch, d_out_offsets, ws, ws_bytes, d_result,
-        d_status, s,
+        d_status, s, cvt,
         // the scan and the plan read the stream's address and size only: the index comes behind them
         [&](const WindowBufs&) { return WindowStream{RangeStream{i8}, (int64_t)size}; },
         [&](WindowStream& src, const WindowBufs& b, const int64_t*& idx_err) {
             return stream_with_index(i8, in_nbytes, cb, p, block_offsets, b.idx, s, src.st, idx_err);
         });
+}
+}  // namespace
+
+int64_t bshuf_decompress_lz4_ragged_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                        size_t block_size, const int64_t* d_starts, const int64_t* d_counts,
+                                        size_t nwindows, size_t max_window, void* out, size_t out_capacity,
+                                        size_t out_pitch, int64_t* d_out_offsets, void* ws, size_t ws_bytes,
+                                        int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
+                                        void* stream) {
+    return ragged_dev(in, in_nbytes, size, elem_size, block_size, d_starts, d_counts, nwindows, max_window, out,
+                      out_capacity, out_pitch, d_out_offsets, ws, ws_bytes, d_result, d_status, block_offsets,
+                      stream, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_ragged_cvt_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                            size_t block_size, const int64_t* d_starts, const int64_t* d_counts,
+                                            size_t nwindows, size_t max_window, void* out, size_t out_capacity,
+                                            size_t out_pitch, int64_t* d_out_offsets, void* ws, size_t ws_bytes,
+                                            int64_t* d_result, int64_t* d_status,
+                                            const uint64_t* block_offsets, void* stream, const bshuf_cvt* cvt) {
+    CvtArgs a;
+    const int64_t r = cvt_check(cvt, elem_size, out, a);
+    if (r) return r;
+    return ragged_dev(in, in_nbytes, size, elem_size, block_size, d_starts, d_counts, nwindows, max_window, out,
+                      out_capacity, out_pitch, d_out_offsets, ws, ws_bytes, d_result, d_status, block_offsets,
+                      stream, &a);
 }
 
 size_t bshuf_decompress_lz4_ragged_set_dev_workspace(size_t max_size, size_t elem_size, size_t block_size,
@@ -1475,12 +1563,12 @@ size_t bshuf_decompress_lz4_ragged_set_dev_workspace(size_t max_size, size_t ele
     return ragged_ws(p, w, 0, nullptr, nullptr);
 }
 
-int64_t bshuf_decompress_lz4_ragged_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
-                                            size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
-                                            const int64_t* d_counts, size_t nwindows, size_t max_window,
-                                            void* out, size_t out_capacity, size_t out_pitch,
-                                            int64_t* d_out_offsets, void* ws, size_t ws_bytes,
-                                            int64_t* d_result, int64_t* d_status, void* stream) {
+namespace {
+int64_t ragged_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size, size_t block_size,
+                       const int64_t* d_ids, const int64_t* d_starts, const int64_t* d_counts, size_t nwindows,
+                       size_t max_window, void* out, size_t out_capacity, size_t out_pitch,
+                       int64_t* d_out_offsets, void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                       void* stream, const CvtArgs* cvt) {
     Plan p;
     int64_t r = make_plan(max_size, elem_size, block_size, p);
     if (r) return r;
@@ -1498,7 +1586,7 @@ int64_t bshuf_decompress_lz4_ragged_set_dev(const void* d_set, size_t count, siz
     if (nwindows == 0 || max_window == 0) return ragged_empty(nwindows, d_out_offsets, d_result, s);
     return ragged_decode(
         p, w, 0, need, d_starts, d_counts, out, out_capacity, out_pitch, d_out_offsets, ws, ws_bytes, d_result,
-        d_status, s,
+        d_status, s, cvt,
         [&](const WindowBufs& b) {
             return WindowSet{(const StreamSetHeader*)d_set,
                              (const StreamSetRec*)((const uint8_t*)d_set + kStreamSetRecs),
@@ -1509,6 +1597,33 @@ int64_t bshuf_decompress_lz4_ragged_set_dev(const void* d_set, size_t count, siz
         },
         // (the set's indexes were made by its build: nothing to rebuild)
         [&](const WindowSet&, const WindowBufs&, const int64_t*&) { return hipSuccess; });
+}
+}  // namespace
+
+int64_t bshuf_decompress_lz4_ragged_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                            size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                            const int64_t* d_counts, size_t nwindows, size_t max_window,
+                                            void* out, size_t out_capacity, size_t out_pitch,
+                                            int64_t* d_out_offsets, void* ws, size_t ws_bytes,
+                                            int64_t* d_result, int64_t* d_status, void* stream) {
+    return ragged_set_dev(d_set, count, max_size, elem_size, block_size, d_ids, d_starts, d_counts, nwindows,
+                          max_window, out, out_capacity, out_pitch, d_out_offsets, ws, ws_bytes, d_result,
+                          d_status, stream, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_ragged_set_cvt_dev(const void* d_set, size_t count, size_t max_size,
+                                                size_t elem_size, size_t block_size, const int64_t* d_ids,
+                                                const int64_t* d_starts, const int64_t* d_counts,
+                                                size_t nwindows, size_t max_window, void* out,
+                                                size_t out_capacity, size_t out_pitch, int64_t* d_out_offsets,
+                                                void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                                void* stream, const bshuf_cvt* cvt) {
+    CvtArgs a;
+    const int64_t r = cvt_check(cvt, elem_size, out, a);
+    if (r) return r;
+    return ragged_set_dev(d_set, count, max_size, elem_size, block_size, d_ids, d_starts, d_counts, nwindows,
+                          max_window, out, out_capacity, out_pitch, d_out_offsets, ws, ws_bytes, d_result,
+                          d_status, stream, &a);
 }
 
 // ---------------------------------------------------------------------------
@@ -1609,7 +1724,7 @@ size_t tile_ws(const Plan& p, const TileShapeH& w, int64_t blocks_end, TileBufs*
 extern "C++" template <class MakeSource, class Worklist>
 int64_t tile_decode(const Plan& p, const TileShapeH& w, int64_t blocks_end, size_t need, const int64_t* d_starts,
                     void* out, void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status, hipStream_t s,
-                    MakeSource make_source, Worklist worklist) {
+                    const CvtArgs* cvt, MakeSource make_source, Worklist worklist) {
     DevBuf own;
     const int64_t r = get_ws(ws, ws_bytes, need, own, s);
     if (r) return r;
@@ -1649,7 +1764,7 @@ int64_t tile_decode(const Plan& p, const TileShapeH& w, int64_t blocks_end, size
             launch_decode_batch(b.segs, nullptr, P, b.blk_seg, L, b.d, s) != hipSuccess)
             return kErrHip;
     }
-    if (launch_tile_gather(src, c, b.pcs, b.ti, b.d.status, tstat, s) != hipSuccess ||
+    if (launch_tile_gather(src, c, b.pcs, b.ti, b.d.status, tstat, s, cvt) != hipSuccess ||
         launch_tile_reduce(tstat, b.ti, K, idx_err, w.K * c.rows * c.rbytes, d_result, s) != hipSuccess)
         return kErrHip;
     return 0;
@@ -1669,11 +1784,11 @@ size_t bshuf_decompress_lz4_tiles_dev_workspace(size_t in_nbytes, size_t size, s
     return tile_ws(p, w, cb > 0 ? cb : 0, nullptr, nullptr);
 }
 
-int64_t bshuf_decompress_lz4_tiles_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
-                                       size_t block_size, const int64_t* d_starts, size_t ntiles, size_t rows,
-                                       size_t cols, size_t pitch, void* out, void* ws, size_t ws_bytes,
-                                       int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
-                                       void* stream) {
+namespace {
+int64_t tiles_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size, size_t block_size,
+                  const int64_t* d_starts, size_t ntiles, size_t rows, size_t cols, size_t pitch, void* out,
+                  void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
+                  void* stream, const CvtArgs* cvt) {
     Plan p;
     int64_t r = make_plan(size, elem_size, block_size, p);
     if (r) return r;
@@ -1689,7 +1804,7 @@ int64_t bshuf_decompress_lz4_tiles_dev(const void* in, size_t in_nbytes, size_t 
     if (w.empty) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
     const uint8_t* i8 = (const uint8_t*)in;
     return tile_decode(
-        p, w, cb, need, d_starts, out, ws, ws_bytes, d_result, d_status, s,
+        p, w, cb, need, d_starts, out, ws, ws_bytes, d_result, d_status, s, cvt,
         // the plan reads the stream's address and size only: the index comes behind it
         [&](const TileBufs&) { return WindowStream{RangeStream{i8}, (int64_t)size}; },
         [&](WindowStream& src, const TileCall& c, const TileBufs& b, const int64_t*& idx_err) {
@@ -1700,6 +1815,28 @@ int64_t bshuf_decompress_lz4_tiles_dev(const void* in, size_t in_nbytes, size_t 
             if (e != hipSuccess) return e;
             return launch_range_worklist(src.st, b.segs, b.pcs, P, P, 0, c.Mg, b.d.offs, s);
         });
+}
+}  // namespace
+
+int64_t bshuf_decompress_lz4_tiles_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                       size_t block_size, const int64_t* d_starts, size_t ntiles, size_t rows,
+                                       size_t cols, size_t pitch, void* out, void* ws, size_t ws_bytes,
+                                       int64_t* d_result, int64_t* d_status, const uint64_t* block_offsets,
+                                       void* stream) {
+    return tiles_dev(in, in_nbytes, size, elem_size, block_size, d_starts, ntiles, rows, cols, pitch, out, ws,
+                     ws_bytes, d_result, d_status, block_offsets, stream, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_tiles_cvt_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                           size_t block_size, const int64_t* d_starts, size_t ntiles,
+                                           size_t rows, size_t cols, size_t pitch, void* out, void* ws,
+                                           size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                           const uint64_t* block_offsets, void* stream, const bshuf_cvt* cvt) {
+    CvtArgs a;
+    const int64_t r = cvt_check(cvt, elem_size, out, a);
+    if (r) return r;
+    return tiles_dev(in, in_nbytes, size, elem_size, block_size, d_starts, ntiles, rows, cols, pitch, out, ws,
+                     ws_bytes, d_result, d_status, block_offsets, stream, &a);
 }
 
 size_t bshuf_decompress_lz4_tiles_set_dev_workspace(size_t max_size, size_t elem_size, size_t block_size,
@@ -1712,11 +1849,11 @@ size_t bshuf_decompress_lz4_tiles_set_dev_workspace(size_t max_size, size_t elem
     return tile_ws(p, w, 0, nullptr, nullptr);
 }
 
-int64_t bshuf_decompress_lz4_tiles_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
-                                           size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
-                                           size_t ntiles, size_t rows, size_t cols, size_t pitch, void* out,
-                                           void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
-                                           void* stream) {
+namespace {
+int64_t tiles_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size, size_t block_size,
+                      const int64_t* d_ids, const int64_t* d_starts, size_t ntiles, size_t rows, size_t cols,
+                      size_t pitch, void* out, void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                      void* stream, const CvtArgs* cvt) {
     Plan p;
     int64_t r = make_plan(max_size, elem_size, block_size, p);
     if (r) return r;
@@ -1731,7 +1868,7 @@ int64_t bshuf_decompress_lz4_tiles_set_dev(const void* d_set, size_t count, size
     hipStream_t s = (hipStream_t)stream;
     if (w.empty) return dev_fill(d_result, 0, sizeof(int64_t), s) == hipSuccess ? 0 : kErrHip;
     return tile_decode(
-        p, w, 0, need, d_starts, out, ws, ws_bytes, d_result, d_status, s,
+        p, w, 0, need, d_starts, out, ws, ws_bytes, d_result, d_status, s, cvt,
         [&](const TileBufs& b) {
             return WindowSet{(const StreamSetHeader*)d_set,
                              (const StreamSetRec*)((const uint8_t*)d_set + kStreamSetRecs),
@@ -1752,6 +1889,28 @@ int64_t bshuf_decompress_lz4_tiles_set_dev(const void* d_set, size_t count, size
             wc.Mw = c.Mg;
             return launch_window_set_worklist(src, wc, b.segs, b.pcs, b.d.offs, s);
         });
+}
+}  // namespace
+
+int64_t bshuf_decompress_lz4_tiles_set_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                           size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                           size_t ntiles, size_t rows, size_t cols, size_t pitch, void* out,
+                                           void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                           void* stream) {
+    return tiles_set_dev(d_set, count, max_size, elem_size, block_size, d_ids, d_starts, ntiles, rows, cols, pitch,
+                         out, ws, ws_bytes, d_result, d_status, stream, nullptr);
+}
+
+int64_t bshuf_decompress_lz4_tiles_set_cvt_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                               size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                               size_t ntiles, size_t rows, size_t cols, size_t pitch, void* out,
+                                               void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                               void* stream, const bshuf_cvt* cvt) {
+    CvtArgs a;
+    const int64_t r = cvt_check(cvt, elem_size, out, a);
+    if (r) return r;
+    return tiles_set_dev(d_set, count, max_size, elem_size, block_size, d_ids, d_starts, ntiles, rows, cols, pitch,
+                         out, ws, ws_bytes, d_result, d_status, stream, &a);
 }
 
 int64_t bshuf_synth_fill_dev(void* out, size_t n_elem, int gen, uint64_t first, uint64_t seed,

@@ -287,6 +287,31 @@ hipError_t launch_range_edges(const RangeStream& st, const RangePiece* pcs, int6
 hipError_t launch_range_reduce(const int64_t* res, int np, const int64_t* idx_err, int64_t total,
                                int64_t* result, hipStream_t s);
 
+// ---- converting gathers (window_copy.h, span_cvt) --------------------------
+// The *_cvt_dev entries of the window, ragged and tile decodes: every element x
+// of a window or tile lands as (dst kind)fmaf((float)x, scale, offset) instead
+// of as itself.  Only the gather kernel differs -- it is instantiated per
+// (source kind, destination kind) over SpanCvt instead of SpanCopy -- and only
+// where it writes: the plan kernels, the tables, the statuses and the result
+// stay the plain call's, in SOURCE bytes; a piece that the tables place b bytes
+// behind `out` lands b / sizeof(source) * sizeof(destination) bytes behind it.
+// CvtArgs mirrors bshuf_cvt (include/bitshuffle.h), checked by the entry.
+enum { kCvtU8, kCvtI8, kCvtU16, kCvtI16, kCvtU32, kCvtI32, kCvtF32, kCvtSrcKinds };
+enum { kCvtDstF32, kCvtDstF16, kCvtDstBF16, kCvtDstKinds };
+struct CvtArgs {
+    int32_t src, dst;
+    float scale, offset;
+};
+constexpr int cvt_src_size(int kind) { return kind < kCvtU16 ? 1 : kind < kCvtU32 ? 2 : 4; }
+constexpr int cvt_dst_size(int kind) { return kind == kCvtDstF32 ? 4 : 2; }
+// The bytes a gather's lane rule goes by, for n source bytes: the larger of
+// what a window or row reads and what it writes.
+inline int64_t cvt_lane_bytes(const CvtArgs* cvt, int64_t n) {
+    if (!cvt) return n;
+    const int S = cvt_src_size(cvt->src), D = cvt_dst_size(cvt->dst);
+    return D > S ? n / S * D : n;
+}
+
 // ---- window decode (lz4_window.hip) --------------------------------------
 // K windows of the same length at DEVICE-held starts, in one stream
 // (bshuf_decompress_lz4_windows_dev) or each in a stream of a set
@@ -374,10 +399,12 @@ hipError_t launch_window_set_worklist(const WindowSet& src, const WindowCall& c,
 // status[i] (wstat): c.wbytes, or -71 (bad window), -91 (set: the stream's error
 // word), the code of the highest failing block that holds clip bytes (dstat: the
 // decode's per-block status), or -91 (tail not inside the stream); only windows
-// with c.wbytes are copied.
+// with c.wbytes are copied -- with cvt, converted (window i then lands at out + i *
+// window destination elements; the statuses stay source bytes).
 template <class Source>
 hipError_t launch_window_gather(const Source& src, const WindowCall& c, const RangePiece* pcs,
-                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s);
+                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s,
+                                const CvtArgs* cvt = nullptr);
 // *result = -91 when *idx_err (nullptr: no index was rebuilt by the call) is set,
 // else -71 when a window was bad, else the status of the highest-numbered
 // failing window, else total (K * wbytes) -- or, with dtotal, `total` bytes for
@@ -425,7 +452,8 @@ hipError_t launch_ragged_worklist(const Source& src, const RaggedCall& c, Seg* s
 // launch_window_gather's rule, window i's byte count being counts[i] * E.
 template <class Source>
 hipError_t launch_ragged_gather(const Source& src, const RaggedCall& c, const RangePiece* pcs,
-                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s);
+                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s,
+                                const CvtArgs* cvt = nullptr);
 
 // ---- tile decode (lz4_tile.hip) -------------------------------------------
 // K tiles of rows x cols elements at DEVICE-held flat starts, row r of tile i
@@ -467,10 +495,11 @@ hipError_t launch_tile_plan(const Source& src, const TileCall& c, Seg* segs, Ran
 // error word), the code of the highest failing block -- in stream order -- among
 // those that hold an element of the tile (dstat: the decode's per-block
 // status), or -91 (a row reaches a verbatim tail that is not inside the stream);
-// only tiles with rows * rbytes are copied, the others not at all.
+// only tiles with rows * rbytes are copied (with cvt: converted, row r of tile i
+// at out + (i * rows + r) * cols destination elements), the others not at all.
 template <class Source>
 hipError_t launch_tile_gather(const Source& src, const TileCall& c, const RangePiece* pcs, const TileInfo* ti,
-                              const int64_t* dstat, int64_t* tstat, hipStream_t s);
+                              const int64_t* dstat, int64_t* tstat, hipStream_t s, const CvtArgs* cvt = nullptr);
 // A/B of the gather's lanes per row (bshuf_set_variant; values of their own,
 // which no other kernel reads): 16, 64 or 256 whatever the row's bytes.
 constexpr int kTileLanes16 = 1 << 22;

@@ -247,12 +247,12 @@ __global__ __launch_bounds__(256) void k_ragged_worklist(Source src, int64_t Mw,
 }
 
 // T lanes per window, 256 / T windows per workgroup (k_window_gather).
-template <int T, class Source>
+template <int T, class Source, class Op>
 __global__ __launch_bounds__(256) void k_ragged_gather(Source src, RaggedCall c,
                                                        const RangePiece* __restrict__ pcs,
                                                        const WindowTail* __restrict__ wt,
                                                        const int64_t* __restrict__ dstat,
-                                                       int64_t* __restrict__ wstat) {
+                                                       int64_t* __restrict__ wstat, Op op) {
     const int i = (int)(blockIdx.x * (256 / T) + threadIdx.x / T);
     const int t = (int)(threadIdx.x % T);
     if (i >= c.w.K) return;
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void k_ragged_gather(Source src, RaggedCall c,
     int64_t err;
     const RangeStream st = source_stream(src, w, i, err);
     window_gather_one(st, err, w, pcs, i, w.t1 > w.t0 ? c.w.res[i] : 0, dstat + (int64_t)i * c.w.Mw,
-                      w.bad ? 0 : c.counts[i] * c.w.E, wstat, t, T);
+                      w.bad ? 0 : c.counts[i] * c.w.E, wstat, t, T, op, c.w.out);
 }
 
 }  // namespace
@@ -304,15 +304,25 @@ hipError_t launch_ragged_worklist(const Source& src, const RaggedCall& c, Seg* s
 
 template <class Source>
 hipError_t launch_ragged_gather(const Source& src, const RaggedCall& c, const RangePiece* pcs,
-                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s) {
+                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s,
+                                const CvtArgs* cvt) {
     ProfScope prof(names(src).gather, s);
-    // by the longest window a call may hold (launch_window_gather)
-    if (c.w.wbytes <= 2048)
-        hipLaunchKernelGGL((k_ragged_gather<64, Source>), dim3((unsigned)((c.w.K + 3) / 4)), dim3(256), 0, s,
-                           src, c, pcs, wt, dstat, wstat);
+    // by the longest window a call may hold (launch_window_gather, also for a
+    // converting gather: not measured)
+    const bool wave = cvt_lane_bytes(cvt, c.w.wbytes) <= 2048;
+    auto go = [&](auto op) {
+        using Op = decltype(op);
+        if (wave)
+            hipLaunchKernelGGL((k_ragged_gather<64, Source, Op>), dim3((unsigned)((c.w.K + 3) / 4)), dim3(256), 0,
+                               s, src, c, pcs, wt, dstat, wstat, op);
+        else
+            hipLaunchKernelGGL((k_ragged_gather<256, Source, Op>), dim3((unsigned)c.w.K), dim3(256), 0, s, src, c,
+                               pcs, wt, dstat, wstat, op);
+    };
+    if (cvt)
+        cvt_dispatch(*cvt, go);
     else
-        hipLaunchKernelGGL((k_ragged_gather<256, Source>), dim3((unsigned)c.w.K), dim3(256), 0, s, src, c, pcs,
-                           wt, dstat, wstat);
+        go(SpanCopy{});
     return hipGetLastError();
 }
 
@@ -323,7 +333,8 @@ hipError_t launch_ragged_gather(const Source& src, const RaggedCall& c, const Ra
     template hipError_t launch_ragged_worklist(const Source&, const RaggedCall&, Seg*, const RangePiece*,      \
                                                const WindowTail*, uint64_t*, uint32_t*, hipStream_t);          \
     template hipError_t launch_ragged_gather(const Source&, const RaggedCall&, const RangePiece*,              \
-                                             const WindowTail*, const int64_t*, int64_t*, hipStream_t);
+                                             const WindowTail*, const int64_t*, int64_t*, hipStream_t,     \
+                                             const CvtArgs*);
 BSHUF_RAGGED_INST(WindowStream)
 BSHUF_RAGGED_INST(WindowSet)
 #undef BSHUF_RAGGED_INST

@@ -126,11 +126,13 @@ __global__ __launch_bounds__(256) void k_tile_plan(Source src, TileCall c, Seg* 
 // span_copy out of its group's staging area and the tail.  Reads stay inside
 // the tile's staging areas (16-byte granules of areas that are 16-byte aligned
 // and a multiple of 16 long) and its stream, writes inside its slice of out.
-template <int T, class Source>
+// Op: SpanCopy, or SpanCvt for the converting entries (window_copy.h), whose
+// rows land where op.place() puts the plain call's.
+template <int T, class Source, class Op>
 __global__ __launch_bounds__(256) void k_tile_gather(Source src, TileCall c, const RangePiece* __restrict__ pcs,
                                                      const TileInfo* __restrict__ ti,
                                                      const int64_t* __restrict__ dstat,
-                                                     int64_t* __restrict__ tstat) {
+                                                     int64_t* __restrict__ tstat, Op op) {
     __shared__ unsigned long long worst;  // 1 + the highest failing stream block with a tile element
     __shared__ int64_t worst_code;
     const int64_t i = blockIdx.x;
@@ -192,9 +194,9 @@ __global__ __launch_bounds__(256) void k_tile_gather(Source src, TileCall c, con
         const int64_t p = p0 + (c.G == 1 ? 0 : r / c.rg);
         TileRow o;
         tile_row(covered, c.bs, c.E, c.cols, c.pitch, c.rg, info.start, r, pcs[p].b0, o);
-        uint8_t* dst = out + r * c.rbytes;
-        if (o.n > 0) span_copy(c.slots + p * c.slot + o.lo, dst, o.n, t, T);
-        if (o.tail_n > 0) span_copy(tsrc + o.tail_lo, dst + o.n, o.tail_n, t, T);
+        uint8_t* dst = op.place(c.out, out + r * c.rbytes);
+        if (o.n > 0) op.span(c.slots + p * c.slot + o.lo, dst, o.n, t, T);
+        if (o.tail_n > 0) op.tail(tsrc + o.tail_lo, op.behind(dst, o.n), o.tail_n, t, T);
     }
 }
 
@@ -233,7 +235,7 @@ hipError_t launch_tile_plan(const Source& src, const TileCall& c, Seg* segs, Ran
 
 template <class Source>
 hipError_t launch_tile_gather(const Source& src, const TileCall& c, const RangePiece* pcs, const TileInfo* ti,
-                              const int64_t* dstat, int64_t* tstat, hipStream_t s) {
+                              const int64_t* dstat, int64_t* tstat, hipStream_t s, const CvtArgs* cvt) {
     ProfScope prof(names(src).gather, s);
     // Lanes per row, by the row's bytes: 16 up to 1 KiB (16 rows of a workgroup
     // in flight, up to four 16-byte chunks per lane), a wave up to 2 KiB, else
@@ -241,19 +243,32 @@ hipError_t launch_tile_gather(const Source& src, const TileCall& c, const RangeP
     // tiles of 256 x 256 (profiles/tile_decode, tools/tile_bench.py, the lanes
     // forced by bshuf_set_variant kTileLanes16 / 64 / 256): this kernel takes
     // 0.083 / 0.137 / 0.341 ms with 512-byte rows and 0.128 / 0.156 / 0.430 ms
-    // with 1024-byte rows.  Longer rows were not measured.
+    // with 1024-byte rows.  Longer rows were not measured.  A converting gather
+    // goes by the larger of the row's source and destination bytes
+    // (cvt_lane_bytes), the same thresholds: not measured.
     const int v = tuning_variant();
-    int T = c.rbytes <= 1024 ? 16 : c.rbytes <= 2048 ? 64 : 256;
+    const int64_t lb = cvt_lane_bytes(cvt, c.rbytes);
+    int T = lb <= 1024 ? 16 : lb <= 2048 ? 64 : 256;
     if (v == kTileLanes16) T = 16;
     if (v == kTileLanes64) T = 64;
     if (v == kTileLanes256) T = 256;
     const dim3 grid((unsigned)c.K), block(256);
-    if (T == 16)
-        hipLaunchKernelGGL((k_tile_gather<16, Source>), grid, block, 0, s, src, c, pcs, ti, dstat, tstat);
-    else if (T == 64)
-        hipLaunchKernelGGL((k_tile_gather<64, Source>), grid, block, 0, s, src, c, pcs, ti, dstat, tstat);
+    auto go = [&](auto op) {
+        using Op = decltype(op);
+        if (T == 16)
+            hipLaunchKernelGGL((k_tile_gather<16, Source, Op>), grid, block, 0, s, src, c, pcs, ti, dstat, tstat,
+                               op);
+        else if (T == 64)
+            hipLaunchKernelGGL((k_tile_gather<64, Source, Op>), grid, block, 0, s, src, c, pcs, ti, dstat, tstat,
+                               op);
+        else
+            hipLaunchKernelGGL((k_tile_gather<256, Source, Op>), grid, block, 0, s, src, c, pcs, ti, dstat, tstat,
+                               op);
+    };
+    if (cvt)
+        cvt_dispatch(*cvt, go);
     else
-        hipLaunchKernelGGL((k_tile_gather<256, Source>), grid, block, 0, s, src, c, pcs, ti, dstat, tstat);
+        go(SpanCopy{});
     return hipGetLastError();
 }
 
@@ -261,9 +276,9 @@ template hipError_t launch_tile_plan(const WindowStream&, const TileCall&, Seg*,
                                      hipStream_t);
 template hipError_t launch_tile_plan(const WindowSet&, const TileCall&, Seg*, RangePiece*, TileInfo*, hipStream_t);
 template hipError_t launch_tile_gather(const WindowStream&, const TileCall&, const RangePiece*, const TileInfo*,
-                                       const int64_t*, int64_t*, hipStream_t);
+                                       const int64_t*, int64_t*, hipStream_t, const CvtArgs*);
 template hipError_t launch_tile_gather(const WindowSet&, const TileCall&, const RangePiece*, const TileInfo*,
-                                       const int64_t*, int64_t*, hipStream_t);
+                                       const int64_t*, int64_t*, hipStream_t, const CvtArgs*);
 
 hipError_t launch_tile_reduce(const int64_t* tstat, const TileInfo* ti, int K, const int64_t* idx_err,
                               int64_t total, int64_t* result, hipStream_t s) {

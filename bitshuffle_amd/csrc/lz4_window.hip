@@ -92,14 +92,14 @@ __global__ __launch_bounds__(256) void k_window_set_worklist(WindowSet src, int6
     range_worklist_piece(st, segs + p, pc, first, wl);
 }
 
-// T lanes per window, 256 / T windows per workgroup; the status and the copy:
-// window_gather_one (window_copy.h).
-template <int T, class Source>
+// T lanes per window, 256 / T windows per workgroup; the status and the copy
+// (Op: SpanCopy) or the conversion (SpanCvt): window_gather_one (window_copy.h).
+template <int T, class Source, class Op>
 __global__ __launch_bounds__(256) void k_window_gather(Source src, WindowCall c,
                                                        const RangePiece* __restrict__ pcs,
                                                        const WindowTail* __restrict__ wt,
                                                        const int64_t* __restrict__ dstat,
-                                                       int64_t* __restrict__ wstat) {
+                                                       int64_t* __restrict__ wstat, Op op) {
     const int i = (int)(blockIdx.x * (256 / T) + threadIdx.x / T);
     const int t = (int)(threadIdx.x % T);
     if (i >= c.K) return;
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void k_window_gather(Source src, WindowCall c,
     int64_t err;
     const RangeStream st = source_stream(src, w, i, err);
     window_gather_one(st, err, w, pcs, i, w.t1 > w.t0 ? c.res[i] : 0, dstat + (int64_t)i * c.Mw, c.wbytes,
-                      wstat, t, T);
+                      wstat, t, T, op, c.out);
 }
 
 __global__ __launch_bounds__(256) void k_stream_set_status(StreamSetRec* __restrict__ recs,
@@ -169,17 +169,28 @@ hipError_t launch_window_set_worklist(const WindowSet& src, const WindowCall& c,
 
 template <class Source>
 hipError_t launch_window_gather(const Source& src, const WindowCall& c, const RangePiece* pcs,
-                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s) {
+                                const WindowTail* wt, const int64_t* dstat, int64_t* wstat, hipStream_t s,
+                                const CvtArgs* cvt) {
     ProfScope prof(names(src).gather, s);
     // a wave per window up to 2 KiB (two 16-byte chunks per lane), else a
     // workgroup: a short window would leave most of a workgroup's four waves
-    // with nothing to copy
-    if (c.wbytes <= 2048)
-        hipLaunchKernelGGL((k_window_gather<64, Source>), dim3((unsigned)((c.K + 3) / 4)), dim3(256), 0, s, src,
-                           c, pcs, wt, dstat, wstat);
+    // with nothing to copy.  A converting gather goes by the larger of the
+    // window's source and destination bytes (cvt_lane_bytes), so that a lane
+    // of the wave has at most two chunks to store: not measured.
+    const bool wave = cvt_lane_bytes(cvt, c.wbytes) <= 2048;
+    auto go = [&](auto op) {
+        using Op = decltype(op);
+        if (wave)
+            hipLaunchKernelGGL((k_window_gather<64, Source, Op>), dim3((unsigned)((c.K + 3) / 4)), dim3(256), 0, s,
+                               src, c, pcs, wt, dstat, wstat, op);
+        else
+            hipLaunchKernelGGL((k_window_gather<256, Source, Op>), dim3((unsigned)c.K), dim3(256), 0, s, src, c,
+                               pcs, wt, dstat, wstat, op);
+    };
+    if (cvt)
+        cvt_dispatch(*cvt, go);
     else
-        hipLaunchKernelGGL((k_window_gather<256, Source>), dim3((unsigned)c.K), dim3(256), 0, s, src, c, pcs, wt,
-                           dstat, wstat);
+        go(SpanCopy{});
     return hipGetLastError();
 }
 
@@ -188,9 +199,9 @@ template hipError_t launch_window_plan(const WindowStream&, const WindowCall&, S
 template hipError_t launch_window_plan(const WindowSet&, const WindowCall&, Seg*, RangePiece*, WindowTail*,
                                        hipStream_t);
 template hipError_t launch_window_gather(const WindowStream&, const WindowCall&, const RangePiece*,
-                                         const WindowTail*, const int64_t*, int64_t*, hipStream_t);
+                                         const WindowTail*, const int64_t*, int64_t*, hipStream_t, const CvtArgs*);
 template hipError_t launch_window_gather(const WindowSet&, const WindowCall&, const RangePiece*,
-                                         const WindowTail*, const int64_t*, int64_t*, hipStream_t);
+                                         const WindowTail*, const int64_t*, int64_t*, hipStream_t, const CvtArgs*);
 
 hipError_t launch_stream_set_status(StreamSetRec* recs, const int64_t* idx_err, int64_t* status, int count,
                                     hipStream_t s) {

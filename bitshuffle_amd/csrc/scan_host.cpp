@@ -2,10 +2,12 @@
 // ticket-stealing arithmetic (ticket_steal.h), of the pipelined encode's
 // segment bounds (pipe_segments.h), of the range decode's piece plan
 // (range_plan.h), of the window decode's plan (window_plan.h), of the tile
-// decode's shape and plan (tile_plan.h) and of the launchers' path decisions
-// (dispatch.h) for the CPU test suite.  Not part of the product library.
+// decode's shape and plan (tile_plan.h), of the converting gathers' span cut
+// (cvt_span.h) and of the launchers' path decisions (dispatch.h) for the CPU
+// test suite.  Not part of the product library.
 #include <stdint.h>
 
+#include "cvt_span.h"
 #include "dispatch.h"
 #include "inplace.h"
 #include "lz4_scan.h"
@@ -201,6 +203,17 @@ extern "C" int bshuf_hostcheck_tile_rows(int64_t count, const int64_t* sizes, in
         for (int j = 0; j < 8; j++) rowsout[8 * r + j] = v[j];
     }
     return bad ? 1 : 0;
+}
+
+// cvt_span.h as span_cvt (window_copy.h) uses it: a span of n elements of S
+// bytes whose source starts at byte address src and whose destination, of D-byte
+// elements, at dst (only their low 4 bits matter).  out[6]: head, nu, nc, tail,
+// ue, r.
+extern "C" void bshuf_hostcheck_cvt_span(uint32_t src, uint32_t dst, int S, int D, int64_t n, int64_t* out) {
+    bshuf::CvtSpan p;
+    bshuf::cvt_span_plan(src, dst, S, D, n, p);
+    const int64_t v[6] = {p.head, p.nu, p.nc, p.tail, p.ue, p.r};
+    for (int i = 0; i < 6; i++) out[i] = v[i];
 }
 
 // dispatch.h as the launchers use it.  The constants, out[14]: kTableBytes,

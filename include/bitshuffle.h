@@ -384,6 +384,83 @@ int64_t bshuf_decompress_lz4_tiles_set_dev(const void* d_set, size_t count, size
                                            void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
                                            void* stream);
 
+/* ---- decode to float: the window, ragged and tile decodes with a fused cast,
+ * scale and offset (additive) ----
+ *
+ * Each of the six entries above has a converting twin, *_cvt_dev, with the same
+ * arguments and a trailing `const bshuf_cvt* cvt` (a HOST pointer, read during
+ * the call; scale and offset become kernel arguments, so a captured call keeps
+ * them).  An element x of the stream lands in `out` as
+ *
+ *     y32 = fmaf((float)x, scale, offset)   one fp32 fused multiply-add
+ *     y   = y32                             dst BSHUF_CVT_F32
+ *         = (half)y32 / (bfloat16)y32       dst BSHUF_CVT_F16 / BSHUF_CVT_BF16
+ *
+ * every conversion rounding to nearest even, (float)x being the identity for a
+ * float source, a 16-bit result overflowing to infinity.  cvt->src names the
+ * stream's element type and must have elem_size bytes (so elem_size is 1, 2 or
+ * 4); cvt->dst names the type of `out`.
+ *
+ * `out`, out_capacity, out_pitch and the d_out_offsets are in DESTINATION
+ * elements: window i lands at out + i * window * sizeof(dst), row r of tile i at
+ * out + ((i * rows + r) * cols) * sizeof(dst), a ragged window at out + off[i] *
+ * sizeof(dst) (or i * out_pitch), and `out` must be aligned to sizeof(dst).  A
+ * window or tile that the plain call would not write leaves its
+ * destination-sized slice of `out` untouched.  Everything else is the plain
+ * entry's: which windows and tiles are bad, d_status and *d_result -- which go
+ * on counting SOURCE bytes (window * elem_size, rows * cols * elem_size, off[K]
+ * * elem_size), so a caller's checks do not change -- the host errors, the
+ * capture rules and the workspace, which the plain entry's _workspace function
+ * sizes.  Only the kernel that copies the decoded elements out differs.
+ *
+ * Host errors of their own, all -71 with nothing enqueued: cvt NULL, a kind
+ * that is none of the ones below, a source kind whose size is not elem_size
+ * (every elem_size but 1, 2 and 4), an `out` not aligned to sizeof(dst). */
+typedef struct bshuf_cvt {
+    int32_t src, dst;    /* BSHUF_CVT_* source kind, destination kind */
+    float scale, offset;
+} bshuf_cvt;
+enum { /* source kinds */
+    BSHUF_CVT_U8, BSHUF_CVT_I8, BSHUF_CVT_U16, BSHUF_CVT_I16, BSHUF_CVT_U32, BSHUF_CVT_I32, BSHUF_CVT_F32_SRC
+};
+enum { /* destination kinds */
+    BSHUF_CVT_F32, BSHUF_CVT_F16, BSHUF_CVT_BF16
+};
+int64_t bshuf_decompress_lz4_windows_cvt_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                             size_t block_size, const int64_t* d_starts, size_t nwindows,
+                                             size_t window, void* out, void* ws, size_t ws_bytes,
+                                             int64_t* d_result, int64_t* d_status,
+                                             const uint64_t* block_offsets, void* stream,
+                                             const bshuf_cvt* cvt);
+int64_t bshuf_decompress_lz4_windows_set_cvt_dev(const void* d_set, size_t count, size_t max_size,
+                                                 size_t elem_size, size_t block_size, const int64_t* d_ids,
+                                                 const int64_t* d_starts, size_t nwindows, size_t window,
+                                                 void* out, void* ws, size_t ws_bytes, int64_t* d_result,
+                                                 int64_t* d_status, void* stream, const bshuf_cvt* cvt);
+int64_t bshuf_decompress_lz4_ragged_cvt_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                            size_t block_size, const int64_t* d_starts, const int64_t* d_counts,
+                                            size_t nwindows, size_t max_window, void* out, size_t out_capacity,
+                                            size_t out_pitch, int64_t* d_out_offsets, void* ws, size_t ws_bytes,
+                                            int64_t* d_result, int64_t* d_status,
+                                            const uint64_t* block_offsets, void* stream, const bshuf_cvt* cvt);
+int64_t bshuf_decompress_lz4_ragged_set_cvt_dev(const void* d_set, size_t count, size_t max_size,
+                                                size_t elem_size, size_t block_size, const int64_t* d_ids,
+                                                const int64_t* d_starts, const int64_t* d_counts,
+                                                size_t nwindows, size_t max_window, void* out,
+                                                size_t out_capacity, size_t out_pitch, int64_t* d_out_offsets,
+                                                void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                                void* stream, const bshuf_cvt* cvt);
+int64_t bshuf_decompress_lz4_tiles_cvt_dev(const void* in, size_t in_nbytes, size_t size, size_t elem_size,
+                                           size_t block_size, const int64_t* d_starts, size_t ntiles,
+                                           size_t rows, size_t cols, size_t pitch, void* out, void* ws,
+                                           size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                           const uint64_t* block_offsets, void* stream, const bshuf_cvt* cvt);
+int64_t bshuf_decompress_lz4_tiles_set_cvt_dev(const void* d_set, size_t count, size_t max_size, size_t elem_size,
+                                               size_t block_size, const int64_t* d_ids, const int64_t* d_starts,
+                                               size_t ntiles, size_t rows, size_t cols, size_t pitch, void* out,
+                                               void* ws, size_t ws_bytes, int64_t* d_result, int64_t* d_status,
+                                               void* stream, const bshuf_cvt* cvt);
+
 /* ---- batched device entry points (additive) ----
  *
  * `count` independent framed streams per call, all with the same elem_size and
