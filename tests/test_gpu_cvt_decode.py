@@ -20,6 +20,10 @@ front and behind, which must come back untouched, as must every window or tile
 that is refused or fails.  Statuses and results are compared word for word
 with the plain entry's on the same arguments: they stay in source bytes.
 
+Which VALUES meet the arithmetic on which path of the span routine -- signed
+zeros, subnormals, ties, overflow edges, non-finite sources, 32-bit integers
+with a scale -- is tests/test_gpu_cvt_values.py's part.
+
 Not expressible from Python and so checked at the C entry only: cvt == NULL and
 a misaligned `out` (torch refuses to make such a view)."""
 import ctypes
